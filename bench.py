@@ -34,6 +34,7 @@ HBM_PEAK = 8.0e12         # B/s, MI355X_MICROARCH.md "HBM3E peak BW"
 FP64_MFMA_PEAK = 78.6e12  # FLOP/s dense fp64 matrix (MI355X_MICROARCH.md / AMD spec; tools/mfma_probe measures 75-77 on the box)
 FLOPS_PER_EVAL = 2 * M * D + 3 * M + 2 * D  # forward + isotropic log-like + identity prior: 134 272
 BYTES_PER_EVAL_STEPS = 8 * D + 8 + (8 * D + 24 + 1)  # k_mh_steps HBM: increment row + uniform in, record out = 1 057 B
+DUMP_CHAINS = 512         # --dump-outputs: chains sampled (seeded) from the last step's records: 512 x (100 x 67 + 64 x 64) doubles = 44 MB
 
 
 def parse_args():
@@ -61,6 +62,10 @@ def parse_args():
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` block (the other BASELINE configurations at full chain counts, each with its own "
                          "roofline: tools/bench_configs.py; rank 0 at N = 1 only, after the headline is measured, ~10 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0's chains, a fixed "
+                         "sample of %d of them, float64 / float32, under 64 MB) so that two builds can be compared output for output"
+                         % DUMP_CHAINS)
     return ap.parse_args()
 
 
@@ -354,6 +359,8 @@ def main():
     dt = tdist.reduce_scalar(time.perf_counter() - t0, "max", dev)
     prof = eng.profile()
     eng.set_profiling(False)
+    if args.dump_outputs and rank == 0:  # before the ESS window, which runs on and reuses the record buffers
+        dump_outputs(args.dump_outputs, eng, params, stats, acc, T_timed)
 
     evals = world * N * T_timed
     out = {
@@ -459,6 +466,28 @@ def main():
 
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, eng, params, stats, acc, T_timed):
+    """The last timed step's results for a fixed, seeded sample of the chains: the records run() hands its caller (params
+    [PERIOD, S, D], stats [PERIOD, S, 3] = log-prior / log-likelihood / log-posterior, accepted [PERIOD, S] as 0 / 1) and the
+    proposal covariance the step's adaptation left in use ([S, D, D])."""
+    import numpy as np
+    import torch
+
+    N = params.shape[1]
+    idx = np.sort(np.random.default_rng(0).choice(N, min(N, DUMP_CHAINS), replace=False))
+    rows, sel = slice(T_timed - PERIOD, T_timed), torch.from_numpy(idx).to(params.device)
+    outs = {"params": params[rows].index_select(1, sel).cpu().numpy(),
+            "stats": stats[rows].index_select(1, sel).cpu().numpy(),
+            "accepted": acc[rows].index_select(1, sel).cpu().numpy().astype(np.float32),
+            "proposal_cov": eng.proposal_state()["C"][idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    sys.stderr.write("[bench] --dump-outputs: %s (%d of %d chains, %.1f MB)\n"
+                     % (", ".join("%s%s" % (k, list(v.shape)) for k, v in outs.items()), len(idx), N,
+                        sum(v.nbytes for v in outs.values()) / 1e6))
 
 
 def ess_section(args, eng, diagnostics, params, stats, acc, rows, N, T_timed, dt, world, local_rank, burnin):

@@ -106,6 +106,27 @@ def test_bench_odd_small_arguments(argv):
     assert out["steps"] == int(argv[1]) and out["value"] > 0 and "roofline" in out
 
 
+def test_bench_dumps_the_last_steps_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's records and proposal covariances for a fixed sample of chains, float32 / float64,
+    under 64 MB, the same on a second run with the same arguments; --steps sets the number of timed steps"""
+    argv = ["--steps", "3", "--warmup", "1", "--chains", "1024", "--pilot", "200", "--burnin", "300", "--ess-iterations", "0",
+            "--no-cpu-baseline", "--no-configs"]
+    dumps = []
+    for run in ("a", "b"):
+        out = _run_bench(argv + ["--dump-outputs", str(tmp_path / run)])
+        assert out["steps"] == 3 and out["kernel_ms"]["k_mh_steps"]["launches"] == 3
+        dumps.append({f[:-4]: np.load(str(tmp_path / run / f)) for f in sorted(os.listdir(str(tmp_path / run)))})
+    a, b = dumps
+    assert sorted(a) == ["accepted", "params", "proposal_cov", "stats"]
+    assert a["params"].shape == (100, 512, 64) and a["stats"].shape == (100, 512, 3) and a["accepted"].shape == (100, 512)
+    assert a["proposal_cov"].shape == (512, 64, 64)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert set(np.unique(a["accepted"])) <= {0.0, 1.0} and np.all(np.isfinite(a["stats"]))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` from a bare shell: two ranks on this one GPU (gloo rehearsal of the RCCL path)"""
     env = {"TINYDA_BENCH_ONE_GPU": "1"}
