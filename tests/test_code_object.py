@@ -49,7 +49,6 @@ HOT = {
 #                              in registers: with them the TWO-level instance spilled 385)
 #   k_ml_steps<64,*,4,true>    its instances for hierarchies with a dense observation covariance on some level (round 4)
 KNOWN_SPILLERS = {
-    "_ZN3tda13k_adapt_splitILi64EEE": 8,  # (TINYDA_ADAPT_SPLIT=1, an A/B switch: the moment recursion on two waves per chain at three waves per SIMD)
     "_ZN3tda10k_ml_stepsILi64ELi4ELi4ELb0EEE": 8,
     "_ZN3tda10k_ml_stepsILi64ELi5ELi4ELb0EEE": 56, "_ZN3tda10k_ml_stepsILi64ELi6ELi4ELb0EEE": 100,  # (five / six levels, round 5: 51 / 95; no spill at 8 .. 32 parameters)
     "_ZN3tda10k_ml_stepsILi128ELi3ELi4ELb0EEE": 4, "_ZN3tda10k_ml_stepsILi128ELi4ELi4ELb0EEE": 48,  # (MLDA above 64 parameters, round 5: 2 / 44; the two-level instance spills nothing)

@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _probe(what, env_extra, tmp_path, tag):
     out = str(tmp_path / ("%s_%s.npz" % (what, tag)))
     env = dict(os.environ)
-    for k in ("TINYDA_DA_LEAN", "TINYDA_DZ_WAVE", "TINYDA_DZ_PIPELINE", "TINYDA_AEMD_FUSED", "TINYDA_FUSE_CHOL_APPLY", "TINYDA_CHOL_BLOCKED",
-              "TINYDA_FUSE_ADAPT_CHOL", "TINYDA_ADAPT_SPLIT", "TINYDA_ADAPT_CIRC", "TINYDA_AEM_BASE", "TINYDA_DZ_FUSED", "TINYDA_ML_SPLIT", "TINYDA_DA_R224", "TINYDA_AM_DEFER", "TINYDA_ML_PREDRAW", "TINYDA_AEM_PRE"):
+    for k in ("TINYDA_DA_LEAN", "TINYDA_DZ_WAVE", "TINYDA_AEMD_FUSED", "TINYDA_FUSE_CHOL_APPLY",
+              "TINYDA_FUSE_ADAPT_CHOL", "TINYDA_ADAPT_CIRC", "TINYDA_AEM_BASE", "TINYDA_DZ_FUSED", "TINYDA_ML_SPLIT", "TINYDA_DA_R224", "TINYDA_AM_DEFER", "TINYDA_ML_PREDRAW", "TINYDA_AEM_PRE"):
         env.pop(k, None)
     env.update(env_extra)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "switch_probe.py"), what, out], cwd=ROOT, env=env,
@@ -57,23 +57,28 @@ def test_draws_on_the_second_stream_change_nothing(what, tmp_path):
         assert np.array_equal(on[k], plain[k]), "%s differs between the two entry points (%s)" % (k, what)
 
 
+def _host_factor(C):
+    """the lower Cholesky factor of every chain's matrix, on the host"""
+    return np.stack([np.linalg.cholesky(c) for c in C])
+
+
 @pytest.mark.parametrize("what", ["am", "am_ragged"])
 def test_fused_swap_and_increments_equal_the_two_launches(what, tmp_path):
     """k_chol_apply (covariance swap + the next block's increments in one launch, the factor read back from L2 by the wave that
     wrote it) against k_chol followed by k_apply (TINYDA_FUSE_CHOL_APPLY=0): the same arithmetic, bit for bit, over five swaps"""
-    off = {"TINYDA_CHOL_BLOCKED": "0"}  # the row-per-lane factorisation in both: the same arithmetic, so the same bits
-    fused, split = _probe(what, off, tmp_path, "fused"), _probe(what, dict(off, TINYDA_FUSE_CHOL_APPLY="0"), tmp_path, "split")
+    row = what.replace("am", "am_d24", 1)  # 24 parameters: the row-per-lane factorisation of the 32-parameter instances
+    fused, split = _probe(row, {}, tmp_path, "fused"), _probe(row, {"TINYDA_FUSE_CHOL_APPLY": "0"}, tmp_path, "split")
     for k in fused:
         assert np.array_equal(fused[k], split[k]), k
     assert 0.02 < fused["acc0"].mean() < 0.98 and np.abs(fused["C"]).max() > 0
-    # the blocked factorisation (default at 64 parameters) sums in a different order and takes its pivots' reciprocal square roots
-    # from the hardware estimate + one correction: the same factor to rounding, the same decisions
+    # 64 parameters: the blocked factorisation sums in another order than LAPACK and takes its pivots' reciprocal square roots from
+    # the hardware estimate + one correction -- the factor of Sigma at the last swap (proposal.py: C = get_sigma()) to rounding
     blk = _probe(what, {}, tmp_path, "blocked")
-    assert np.array_equal(blk["acc0"], fused["acc0"])
-    # (the probe swaps after 60 steps in 64 dimensions: its first covariances are rank-deficient up to the eps I term, so their
-    # factors -- and the states proposed from them -- move by the rounding error times a large condition number)
-    for k, tol in (("params0", 1e-8), ("stats0", 1e-6), ("C", 1e-8), ("sigma", 1e-8), ("scaling", 1e-12)):
-        np.testing.assert_allclose(blk[k], fused[k], rtol=tol, atol=tol * np.abs(fused[k]).max(), err_msg=k)
+    assert 0.02 < blk["acc0"].mean() < 0.98
+    # (the device factor L is read back as C = L L^T; the probe's Sigma comes from a few hundred states in 64 dimensions, so the two
+    # factors differ by the rounding error times its condition number)
+    L, L_host = _host_factor(blk["C"]), _host_factor(blk["sigma_swap"])
+    np.testing.assert_allclose(L, L_host, rtol=1e-8, atol=1e-8 * np.abs(L_host).max())
     blk2 = _probe(what, {"TINYDA_FUSE_CHOL_APPLY": "0"}, tmp_path, "blocked_split")  # k_chol_apply_blk<., false> + k_apply
     assert np.array_equal(blk2["acc0"], blk["acc0"])
     np.testing.assert_allclose(blk2["stats0"], blk["stats0"], rtol=1e-6)
@@ -83,11 +88,6 @@ def test_fused_swap_and_increments_equal_the_two_launches(what, tmp_path):
     two = _probe(what, {"TINYDA_FUSE_ADAPT_CHOL": "0"}, tmp_path, "two_launches")
     for k in blk:
         assert np.array_equal(blk[k], two[k]), "one-launch boundary changed %s" % k
-    # round 5: the recursion's ten tiles dealt to two waves per chain (k_adapt_split, TINYDA_ADAPT_SPLIT=1): the same operations per
-    # element -- bitwise
-    spl = _probe(what, {"TINYDA_FUSE_ADAPT_CHOL": "0", "TINYDA_ADAPT_SPLIT": "1"}, tmp_path, "split_recursion")
-    for k in blk:
-        assert np.array_equal(blk[k], spl[k]), "k_adapt_split changed %s" % k
     # round 5, late: the diagonal blocks of Sigma as circulant slots (adapt_am_chain_c64, the default at 64 parameters; 264 instead of
     # 320 operations per state) against full diagonal tiles (TINYDA_ADAPT_CIRC=0), in the one-launch boundary and in k_adapt alone: the
     # same operations per element -- bitwise
@@ -163,20 +163,16 @@ def test_error_model_outputs_on_the_matrix_cores_agree(what, tmp_path):
 @pytest.mark.parametrize("what", ["dream", "dream_ragged"])
 def test_dream_kernel_choices_agree(what, tmp_path):
     """the fused block (draws + steps in one launch) against k_dreamz_draw -> k_dreamz_steps_wave (TINYDA_DZ_FUSED=0): bitwise;
-    k_dreamz_steps_wave against the 16-chain tile kernel (TINYDA_DZ_WAVE=0), and the draw-ahead pipeline
-    (TINYDA_DZ_PIPELINE=1: same sums in the same order, bitwise)"""
+    k_dreamz_steps_wave against the 16-chain tile kernel (TINYDA_DZ_WAVE=0)"""
     fused = _probe(what, {}, tmp_path, "fused")  # (512 chains: draws and steps of a block in ONE launch, k_dreamz_draw<32, false, true>)
     wave = _probe(what, {"TINYDA_DZ_FUSED": "0"}, tmp_path, "wave")
     tile = _probe(what, {"TINYDA_DZ_FUSED": "0", "TINYDA_DZ_WAVE": "0"}, tmp_path, "tile")
-    pipe = _probe(what, {"TINYDA_DZ_FUSED": "0", "TINYDA_DZ_PIPELINE": "1"}, tmp_path, "pipe")
     for k in ("acc0", "stats0", "params0", "pCR"):
         assert np.array_equal(fused[k], wave[k]), "the fused block changed %s" % k
     assert np.array_equal(wave["acc0"], tile["acc0"])
     np.testing.assert_allclose(wave["stats0"], tile["stats0"], rtol=1e-10)
     np.testing.assert_allclose(wave["params0"], tile["params0"], rtol=1e-12, atol=1e-14)
     np.testing.assert_allclose(wave["pCR"], tile["pCR"], rtol=1e-9)
-    for k in ("acc0", "stats0", "params0", "pCR"):
-        assert np.array_equal(wave[k], pipe[k]), "draw-ahead pipeline changed %s" % k
     assert 0.01 < wave["acc0"].mean() < 0.9
 
 

@@ -33,6 +33,12 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// an integer switch from the environment (atoi of its value), dflt when unset; callers keep the answer in a static const
+int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
 #define HIP_TRY(expr)                                                                              \
   do {                                                                                             \
     hipError_t _e = (expr);                                                                        \
@@ -433,9 +439,6 @@ struct tda_engine {
   int64_t pending_steps = 0;  // shared mode: steps whose states are in blk_hist but not yet appended
   DevBuf<double> arch, zsum, zsq, dz_pCR, dz_LCR, dz_Delta, dz_coef, dz_epsm, theta_prev, blk_states, blk_hist;
   DevBuf<int32_t> dz_ridx, dz_mcr_last;
-  DevBuf<double> dz_coef2, dz_epsm2, dz_u2;  // second set of draw outputs (shared DREAM: block b + 1 is drawn under block b's steps)
-  DevBuf<int32_t> dz_ridx2;
-  hipEvent_t ev_dz_adapt = nullptr;
   DevBuf<double> dz_partial;
   DevBuf<int32_t> rp_r, rp_mcr, rp_forced;
   DevBuf<double> rp_sub, rp_e, rp_eps, rp_u;
@@ -462,16 +465,11 @@ inline int am_tiles_rt(int dp) {
   return t * (t + 1) / 2;
 }
 
-int g_steps_waves = 0;  // 0 = decide per launch; TINYDA_STEPS_WAVES=4|8 pins it (A/B measurements)
-
 template <int DPAD>
 void launch_steps(const StepArgs& a, int64_t tiles, size_t lds, hipStream_t st) {
-  if (g_steps_waves == 0) {
-    const char* ev = getenv("TINYDA_STEPS_WAVES");
-    g_steps_waves = (ev && atoi(ev) == 4) ? 4 : 8;
-  }
+  static const bool eight_ok = env_int("TINYDA_STEPS_WAVES", 8) != 4;  // TINYDA_STEPS_WAVES=4: four waves per tile (A/B measurements)
   // dense noise keeps a 128 KiB residual tile and long MFMA chains per wave: 4 waves (512 registers) there
-  const bool eight = g_steps_waves == 8 && a.lv.noise_kind != TDA_NOISE_DENSE;
+  const bool eight = eight_ok && a.lv.noise_kind != TDA_NOISE_DENSE;
   const bool ind = a.prop_kind == TDA_PROP_INDEPENDENCE;
   const bool os = a.prop_kind == TDA_PROP_OWCN && a.mode == MODE_STEP && a.cvec != nullptr;  // per-chain operators from the spectrum of B
   const bool ow = a.prop_kind == TDA_PROP_OWCN && a.mode == MODE_STEP && !os;  // + current-state tile and the state operator in LDS
@@ -517,19 +515,14 @@ template <int DPAD>
 void launch_apply(const ApplyArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_apply<DPAD>, dim3((unsigned)a.NP), dim3(64), 0, st, a);
 }
+// TINYDA_ADAPT_CIRC=0 reaches the tile-form recursion at 64 parameters only through this switch; it stays as the bitwise comparator
+// of the circulant one (tests/test_gpu_switches.py)
 static bool adapt_circ() {
-  static const bool on = !(getenv("TINYDA_ADAPT_CIRC") && atoi(getenv("TINYDA_ADAPT_CIRC")) == 0);
+  static const bool on = env_int("TINYDA_ADAPT_CIRC", 1) != 0;
   return on;
 }
 template <int DPAD>
 void launch_adapt(const AdaptArgs& a, hipStream_t st) {
-  if constexpr (DPAD == 64) {  // TINYDA_ADAPT_SPLIT=1 (A/B): the ten tiles of a chain dealt to two waves, three waves per SIMD (k_adapt_split)
-    static const bool split = getenv("TINYDA_ADAPT_SPLIT") && atoi(getenv("TINYDA_ADAPT_SPLIT")) == 1;
-    if (split && a.do_am && !a.block_moments) {
-      hipLaunchKernelGGL(k_adapt_split<DPAD>, dim3((unsigned)(2 * a.N)), dim3(64), 0, st, a);
-      return;
-    }
-  }
   if (a.do_am && a.block_moments) { hipLaunchKernelGGL(k_adapt_block<DPAD>, dim3((unsigned)a.N), dim3(64), 0, st, a); return; }
   if constexpr (DPAD == 64) {  // TINYDA_ADAPT_CIRC=0 (A/B): the diagonal blocks as full tiles (rounds 2-4)
     if (adapt_circ() && a.do_am) { hipLaunchKernelGGL((k_adapt<DPAD, true>), dim3((unsigned)a.N), dim3(64), 0, st, a); return; }
@@ -539,32 +532,25 @@ void launch_adapt(const AdaptArgs& a, hipStream_t st) {
 template <int DPAD>
 void launch_chol(const CholArgs& a, hipStream_t st) {
   if constexpr (DPAD == 64) {  // the blocked factorisation (k_chol_apply_blk without its second half)
-    static const bool blocked_ok = !(getenv("TINYDA_CHOL_BLOCKED") && atoi(getenv("TINYDA_CHOL_BLOCKED")) == 0);
-    if (blocked_ok) {
-      hipLaunchKernelGGL((k_chol_apply_blk<DPAD, false>), dim3((unsigned)a.N), dim3(64), 0, st, a, ApplyArgs{});
-      return;
-    }
+    hipLaunchKernelGGL((k_chol_apply_blk<DPAD, false>), dim3((unsigned)a.N), dim3(64), 0, st, a, ApplyArgs{});
+  } else {
+    hipLaunchKernelGGL(k_chol<DPAD>, dim3((unsigned)a.N), dim3(64), 0, st, a);
   }
-  hipLaunchKernelGGL(k_chol<DPAD>, dim3((unsigned)a.N), dim3(64), 0, st, a);
 }
 template <int DPAD>
 void launch_chol_apply(const CholArgs& a, const ApplyArgs& ap, hipStream_t st) {
-  if constexpr (DPAD == 64) {  // four 16-column panels: the blocked kernel (TINYDA_CHOL_BLOCKED=0: the row-per-lane one, for A/B measurements)
-    static const bool blocked_ok = !(getenv("TINYDA_CHOL_BLOCKED") && atoi(getenv("TINYDA_CHOL_BLOCKED")) == 0);
-    if (blocked_ok) {
-      hipLaunchKernelGGL(k_chol_apply_blk<DPAD>, dim3((unsigned)ap.NP), dim3(64), 0, st, a, ap);
-      return;
-    }
+  if constexpr (DPAD == 64) {  // four 16-column panels: the blocked kernel
+    hipLaunchKernelGGL(k_chol_apply_blk<DPAD>, dim3((unsigned)ap.NP), dim3(64), 0, st, a, ap);
+  } else {
+    hipLaunchKernelGGL(k_chol_apply<DPAD>, dim3((unsigned)ap.NP), dim3(64), 0, st, a, ap);
   }
-  hipLaunchKernelGGL(k_chol_apply<DPAD>, dim3((unsigned)ap.NP), dim3(64), 0, st, a, ap);
 }
 
 // the period boundary of the single-level AdaptiveMetropolis pipeline in one launch (k_adapt_chol_apply, DPAD = 64 only)
 template <int DPAD>
 bool launch_adapt_chol_apply(const AdaptArgs& aa, const CholArgs& ca, const ApplyArgs& ap, hipStream_t st) {
   if constexpr (DPAD == 64) {
-    static const bool ok = !(getenv("TINYDA_FUSE_ADAPT_CHOL") && atoi(getenv("TINYDA_FUSE_ADAPT_CHOL")) == 0) &&  // A/B switches
-                           !(getenv("TINYDA_CHOL_BLOCKED") && atoi(getenv("TINYDA_CHOL_BLOCKED")) == 0);
+    static const bool ok = env_int("TINYDA_FUSE_ADAPT_CHOL", 1) != 0;  // A/B switch
     if (ok && aa.do_am && !aa.block_moments) {
       if (adapt_circ()) hipLaunchKernelGGL((k_adapt_chol_apply<DPAD, true>), dim3((unsigned)ap.NP), dim3(64), 0, st, aa, ca, ap);
       else hipLaunchKernelGGL((k_adapt_chol_apply<DPAD, false>), dim3((unsigned)ap.NP), dim3(64), 0, st, aa, ca, ap);
@@ -598,7 +584,8 @@ template <>
 void launch_apply<128>(const ApplyArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_wide_apply<WIDE_T>, dim3((unsigned)a.NP), dim3(64), 0, st, wide_apply_args(a));
 }
-// replay mode (and TINYDA_SPLIT_PROPOSE=0): uniforms, the normals as fragments (recorded ones converted, or k_rng<128>), the product
+// the fused proposal (replay mode, the hierarchies' per-block draws): uniforms, the normals as fragments (recorded ones converted,
+// or k_rng<128>), the product
 template <>
 void launch_propose<128>(const ProposeArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_wide_uniforms, dim3((unsigned)(((int64_t)a.S * a.NP + 255) / 256)), dim3(256), 0, st, a);
@@ -694,8 +681,8 @@ inline bool da_lean_eligible(const MLArgs& a) {
   if (a.aem_on == 2 && a.d <= 32) return false;  // (its instances exist for the 64-parameter padding only)
   for (int k = 0; k < a.nlev; ++k)
     if (a.lv[k].noise_kind != 0 && a.lv[k].noise_kind != 1) return false;
-  static const bool off = getenv("TINYDA_DA_LEAN") && atoi(getenv("TINYDA_DA_LEAN")) == 0;  // A/B switch for measurements
-  return !off;
+  static const bool lean_ok = env_int("TINYDA_DA_LEAN", 1) != 0;  // A/B switch for measurements
+  return lean_ok;
 }
 
 // free_regs != nullptr: no launch; *free_regs = the vector registers per SIMD lane that one resident tile of the kernel this call
@@ -705,7 +692,7 @@ inline bool da_lean_eligible(const MLArgs& a) {
 // two-level kernel exists it is launched instead of the plain one (TINYDA_DA_R224=0: never)
 template <int DPAD>
 int launch_ml(const MLArgs& a, int64_t tiles, size_t lds, hipStream_t st, int* free_regs = nullptr, bool lean224 = false) {
-  static const bool r224_ok = !(getenv("TINYDA_DA_R224") && atoi(getenv("TINYDA_DA_R224")) == 0);
+  static const bool r224_ok = env_int("TINYDA_DA_R224", 1) != 0;
   auto regs_left = [&](const void* kern, int waves_per_simd) -> int {
     hipFuncAttributes fa{};
     HIP_TRY(hipFuncGetAttributes(&fa, kern));
@@ -831,10 +818,7 @@ template <int DPAD>
 void launch_dz_steps(const DreamStepArgs& a, size_t lds, hipStream_t st) {
   // the built-in non-linear model under a diagonal prior: chains as lane groups of a wave, no tile, no barriers
   // (TINYDA_DZ_WAVE=0: the 16-chain tile kernel, for A/B measurements)
-  static const bool wave_ok = [] {
-    const char* v = getenv("TINYDA_DZ_WAVE");
-    return !(v && v[0] == '0');
-  }();
+  static const bool wave_ok = env_int("TINYDA_DZ_WAVE", 1) != 0;
   if (wave_ok && a.model == MODEL_ROSENBROCK && a.pr.kind != PRIOR_DENSE) {
     constexpr int CPW = 64 / (DPAD >= 16 ? 16 : DPAD);
     hipLaunchKernelGGL(k_dreamz_steps_wave<DPAD>, dim3((unsigned)(a.NP / CPW)), dim3(64), 0, st, a);
@@ -1262,7 +1246,6 @@ void tda_engine_destroy(tda_engine* e) {
   }
   for (int r = 0; r < tda::MAX_PEERS; ++r)
     if (e->dist_opened[r]) (void)hipIpcCloseMemHandle(e->dist_opened[r]);
-  if (e->ev_dz_adapt) (void)hipEventDestroy(e->ev_dz_adapt);
   if (e->rng_stream) {
     (void)hipStreamSynchronize(e->rng_stream);
     (void)hipStreamDestroy(e->rng_stream);

@@ -131,36 +131,6 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     e->timed.clear();
   }
   const bool ext_model0 = lv.model == MODEL_CALLBACK || lv.model == MODEL_USER;
-  // TINYDA_DZ_PIPELINE=1 (off by default -- measured SLOWER): one process, shared archive appended in place: everything
-  // k_dreamz_draw produces except the archive gather depends on the step counter only (and on pCR / scaling, which change at
-  // adaptation boundaries), so block b + 1 can be drawn on a second stream while block b steps, the step kernel gathering the
-  // archive rows itself (the same sums in the same order: results do not depend on this switch, the sharding-invariance tests
-  // pass either way).  On C4 (8192 chains, d = 32, interval 16) the two kernels do run concurrently but each then takes the sum
-  // of their stand-alone times (draw 52 us and steps 28 us alone, 80-97 us each together: the draw saturates the VALU issue of
-  // every SIMD and the steps' dependent chains wait behind it, s_setprio made no difference) and every block pays ~13 us for
-  // the cross-stream events: 1.00e9 evals/s against 1.19e9 for the plain sequence.
-  // TINYDA_DZ_PIPELINE=2 (experiment, round 4): the same two-stream pipeline with a fixed LAG of one block -- the draws of block
-  // b + 1 see the archive as it was before block b (what distributed.run_shared_dream(overlap=True) gives every rank count), so
-  // they can gather their rows themselves while block b steps: the step kernel stays the pure HBM-bound one.
-  static const int pipe_mode = getenv("TINYDA_DZ_PIPELINE") ? atoi(getenv("TINYDA_DZ_PIPELINE")) : 0;
-  static const bool pipe_ok = pipe_mode == 1 || pipe_mode == 2;
-  const bool pipe_lag = pipe_mode == 2;
-  const bool pipe = pipe_ok && sh && e->auto_append && N == NP && e->pending_steps == 0 && !ext_model0 && !e->dist_ranks;
-  if (pipe && !e->dz_coef2.p) {
-    int rc;
-    if ((rc = e->dz_coef2.alloc((size_t)e->SMAX * NP * DP)) || (rc = e->dz_epsm2.alloc((size_t)e->SMAX * NP * DP)) ||
-        (rc = e->dz_ridx2.alloc((size_t)e->SMAX * NP * 2 * MAX_DELTA)) || (rc = e->dz_u2.alloc((size_t)e->SMAX * NP)))
-      return rc;
-  }
-  if (pipe && !e->rng_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&e->rng_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_rng[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_apply[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_steps[i], hipEventDisableTiming));
-    }
-  }
-  if (pipe && !e->ev_dz_adapt) HIP_TRY(hipEventCreateWithFlags(&e->ev_dz_adapt, hipEventDisableTiming));
   // Shared archive, one process appending its own rows: the exchange points are the CALL-RELATIVE multiples of sync_every -- where
   // the multi-rank driver (distributed.run_shared_dream: one run() per interval, then the all-gather) has them.  A block that an
   // adaptation boundary cuts in two is not an exchange point: the rows of its first half become visible together with the second
@@ -186,8 +156,8 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       return fail(TDA_ERR_INVALID, "distributed archive: a run() call covers at most one exchange interval (%lld steps) and does not cross an adaptation boundary", (long long)K);
     if (e->dz.M0 + (e->dist_steps + e->dist_pending + n_iter) * N > e->arch_cap) return fail(TDA_ERR_INVALID, "archive segment capacity (%lld rows) exceeded", (long long)e->arch_cap);
   }
-  // everything DREAMZ.make_proposal draws for S steps from step t0 on, the archive holding M_base rows: into buffer set `set`
-  auto enqueue_draw = [&](int set, int64_t t0, int64_t M_base, int64_t S, int64_t rp_pos, int64_t exp_pos, bool gather, hipStream_t st, const DreamFuseArgs* fuse = nullptr) {
+  // everything DREAMZ.make_proposal draws for the S steps of the next block
+  auto enqueue_draw = [&](int64_t S, bool gather, const DreamFuseArgs* fuse = nullptr) {
     DreamDrawArgs da{};
     da.N = N;
     da.NP = NP;
@@ -196,21 +166,21 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     da.S = (int)S;
     da.delta = e->dz.delta;
     da.nCR = e->dz.nCR;
-    da.step0 = t0;
-    da.M_base = M_base;
+    da.step0 = e->t;
+    da.M_base = e->arch_rows;
     da.grow = sh ? 0 : 1;
     da.seed = e->cfg.seed;
     da.b = e->dz.b;
     da.b_star = e->dz.b_star;
     da.scaling = e->scaling.p;
     da.pCR = e->dz_pCR.p;
-    da.coef = set ? e->dz_coef2.p : e->dz_coef.p;
-    da.epsm = set ? e->dz_epsm2.p : e->dz_epsm.p;
-    da.ridx = set ? e->dz_ridx2.p : e->dz_ridx.p;
-    da.u = set ? e->dz_u2.p : e->ublk.p;
+    da.coef = e->dz_coef.p;
+    da.epsm = e->dz_epsm.p;
+    da.ridx = e->dz_ridx.p;
+    da.u = e->ublk.p;
     da.mcr_last = e->dz_mcr_last.p;
     if (e->rp_steps) {
-      const size_t o = (size_t)rp_pos * N;
+      const size_t o = (size_t)e->rp_pos * N;
       da.r_rep = e->rp_r.p + o * e->dz.delta * 2;
       da.mcr_rep = e->rp_mcr.p + o;
       da.forced_rep = e->rp_forced.p + o;
@@ -220,8 +190,8 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       da.u_rep = e->rp_u.p + o;
     }
     if (e->exp_steps) {
-      da.eps_export = (e->exp_dev ? e->z_exp : e->z_exp_d.p) + (size_t)exp_pos * N * d;
-      da.u_export = (e->exp_dev ? e->u_exp : e->u_exp_d.p) + (size_t)exp_pos * N;
+      da.eps_export = (e->exp_dev ? e->z_exp : e->z_exp_d.p) + (size_t)e->exp_pos * N * d;
+      da.u_export = (e->exp_dev ? e->u_exp : e->u_exp_d.p) + (size_t)e->exp_pos * N;
     }
     da.arch_shared = gather ? e->arch.p : nullptr;
     if (e->dist_ranks) {
@@ -232,42 +202,25 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       da.dist_ntot = N * e->dist_ranks;
       da.seg = e->dist_seg_dev.p;
     }
-    DISPATCH_DPAD(DP, launch_dz_draw<DPAD>(da, st, fuse));
+    DISPATCH_DPAD(DP, launch_dz_draw<DPAD>(da, e->stream, fuse));
   };
-  int64_t done = 0, blk = 0;
-  if (pipe && n_iter > 0) {
-    // everything queued on the main stream so far (init, earlier run() calls, their adaptation) precedes the first draw
-    HIP_TRY(hipEventRecord(e->ev_dz_adapt, e->stream));
-    HIP_TRY(hipStreamWaitEvent(e->rng_stream, e->ev_dz_adapt, 0));
-    enqueue_draw(0, e->t, e->arch_rows, block_len(e->t, n_iter, 0), e->rp_pos, e->exp_pos, pipe_lag, e->rng_stream);
-    HIP_TRY(hipEventRecord(e->ev_rng[0], e->rng_stream));
-  }
+  int64_t done = 0;
   while (done < n_iter) {
-    const int64_t rows_before = e->arch_rows;  // what this block's proposals could see at most (lagged pipeline: the next block's too)
     const int64_t S = block_len(e->t, n_iter - done, since);
     if (S <= 0) return fail(TDA_ERR_STATE, "shared archive: call archive_take / archive_append before running further");
-    const int set = pipe ? (int)(blk & 1) : 0;
     DreamStepArgs sa{};
     fill_dreamz_step_args(e, sa);
     // BASELINE configs[3] in one launch per block (k_dreamz_draw<32, false, true>): one process appending in place, the built-in
     // Rosenbrock model under a diagonal prior, engine-generated variates; TINYDA_DZ_FUSED=0: the two kernels (same bits)
-    static const bool fused_ok = !(getenv("TINYDA_DZ_FUSED") && atoi(getenv("TINYDA_DZ_FUSED")) == 0);
-    const bool fused = fused_ok && sh && !pipe && !e->dist_ranks && e->auto_append && N == NP && !pending_at_entry && DP == 32 && !ext_model0 &&
+    static const bool fused_ok = env_int("TINYDA_DZ_FUSED", 1) != 0;
+    const bool fused = fused_ok && sh && !e->dist_ranks && e->auto_append && N == NP && !pending_at_entry && DP == 32 && !ext_model0 &&
                        lv.model == MODEL_ROSENBROCK && e->prior_kind != PRIOR_DENSE && !e->rp_steps;
-    if (pipe) {
-      HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_rng[set], 0));
-    } else if (!fused) {
+    if (!fused) {
       ScopedTimer tm(e, 0);
-      enqueue_draw(0, e->t, e->arch_rows, S, e->rp_pos, e->exp_pos, sh, e->stream);
+      enqueue_draw(S, sh);
     }
     sa.S = (int)S;
-    sa.jump_ready = (sh && (!pipe || pipe_lag)) ? 1 : 0;
-    if (set) {
-      sa.coef = e->dz_coef2.p;
-      sa.epsm = e->dz_epsm2.p;
-      sa.ridx = e->dz_ridx2.p;
-      sa.u = e->dz_u2.p;
-    }
+    sa.jump_ready = sh ? 1 : 0;
     const bool ext_model = ext_model0;
     sa.rec_params = p_dev ? o_params + (size_t)done * N * d : (o_params ? e->rec_params.p : nullptr);
     sa.rec_stats = s_dev ? o_stats + (size_t)done * N * 3 : (o_stats ? e->rec_stats.p : nullptr);
@@ -348,7 +301,7 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       fa.rec_acc = sa.rec_acc;
       fa.blk_states = sa.blk_states;
       ScopedTimer tm(e, 1);
-      enqueue_draw(0, e->t, e->arch_rows, S, e->rp_pos, e->exp_pos, true, e->stream, &fa);
+      enqueue_draw(S, true, &fa);
     } else {
       ScopedTimer tm(e, 1);
       DISPATCH_DPAD(DP, launch_dz_steps<DPAD>(sa, lds, e->stream));
@@ -401,20 +354,6 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       }
     }
     if (boundary && !dist) e->k_adapt += 1;
-    if (pipe) {
-      // block b's steps (and its adaptation, if any) are queued: its buffer set is free once they have run.  The draws of
-      // block b + 1 start as soon as the set they overwrite (block b - 1's) is free -- i.e. under block b's steps -- unless
-      // block b ended on an adaptation boundary, whose new pCR / scaling they must see.
-      HIP_TRY(hipEventRecord(e->ev_steps[set], e->stream));
-      if (done + S < n_iter) {
-        const int nset = (int)((blk + 1) & 1);
-        if (blk >= 1) HIP_TRY(hipStreamWaitEvent(e->rng_stream, e->ev_steps[nset], 0));
-        if (boundary) HIP_TRY(hipStreamWaitEvent(e->rng_stream, e->ev_steps[set], 0));
-        enqueue_draw(nset, e->t + S, pipe_lag ? rows_before : e->arch_rows, block_len(e->t + S, n_iter - done - S, since), e->rp_pos + S, e->exp_pos + S,
-                     pipe_lag, e->rng_stream);
-        HIP_TRY(hipEventRecord(e->ev_rng[nset], e->rng_stream));
-      }
-    }
     bool host_copies = false;
     if (o_params && !p_dev) {
       if ((rc = copy_out(e, o_params + (size_t)done * N * d, e->rec_params.p, (size_t)S * N * d * sizeof(double)))) return rc;
@@ -432,7 +371,6 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     if ((rc = progress_mark(e, S, nullptr, 0))) return rc;
     e->t += S;
     done += S;
-    blk += 1;
     if (e->rp_steps) e->rp_pos += S;
     if (e->exp_steps) e->exp_pos += S;
   }

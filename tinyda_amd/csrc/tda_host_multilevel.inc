@@ -18,7 +18,7 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
   for (int k = 0; k < MAXLEV; ++k) cc[k] = e->cnt[k];
   // diagonal error model over a hierarchy of linear levels: base subchains in the fused level kernel (TINYDA_AEMD_FUSED=0: one
   // propose / outputs / accept triple per base step, for A/B measurements); the residual tile of level 0 must fit into LDS
-  static const bool aemd_fused_ok = !(getenv("TINYDA_AEMD_FUSED") && atoi(getenv("TINYDA_AEMD_FUSED")) == 0);
+  static const bool aemd_fused_ok = env_int("TINYDA_AEMD_FUSED", 1) != 0;
   bool all_linear = true;
   for (int k = 0; k < nl; ++k) all_linear = all_linear && e->levels[k].model == MODEL_LINEAR && e->levels[k].Apk.p != nullptr;
   // (LDS of k_ml_steps with only the base level staged: proposal tile, reduction slabs, level 0's data [and weights], prior rows,
@@ -496,7 +496,7 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
   const int period = e->pp.period;
   // dense error model over linear levels, diagonal prior, fixed subchains: the base subchain on k_aem_base_steps (TINYDA_AEM_BASE=0:
   // on k_ml_steps, one pass over every chain's factor per step -- the A/B switch and the path of everything else)
-  static const bool aem_base_ok = !(getenv("TINYDA_AEM_BASE") && atoi(getenv("TINYDA_AEM_BASE")) == 0);
+  static const bool aem_base_ok = env_int("TINYDA_AEM_BASE", 1) != 0;
   // (65 .. 128 parameters: k_ml_steps<128, 1> -- k_aem_base_steps maps a parameter to a lane of its one wave)
   const bool aem_base_kernel = aem_base_ok && (e->aem == TDA_AEM_STATE_INDEPENDENT || e->aem == TDA_AEM_STATE_DEPENDENT) && !e->ext_hier && !e->wide &&
                                !e->randomize && !e->is_dreamz && e->prior_kind != PRIOR_DENSE && e->levels[0].Apk.p != nullptr;
@@ -569,7 +569,7 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
   // fragments (k_rng), increments by k_apply at the head of the block -- or, at an AdaptiveMetropolis swap, by the launch that
   // folds the block's states into the moments and factors the new covariance (k_adapt_chol_apply), as in the single-level pipeline.
   // TINYDA_ML_SPLIT=0 / 1: never / always (A/B measurements).
-  static const int ml_split_env = getenv("TINYDA_ML_SPLIT") ? atoi(getenv("TINYDA_ML_SPLIT")) : -1;  // 0: never, 1: always, unset: by registers
+  static const int ml_split_env = env_int("TINYDA_ML_SPLIT", -1);  // 0: never, 1: always, unset: by registers
   const bool ml_direct = e->L_identity;
   bool ml_split = ml_split_env != 0 && !e->rep_steps && !e->ext_hier && !e->is_dreamz && !e->aem &&
                   (e->pp.kind == TDA_PROP_GRW || e->pp.kind == TDA_PROP_PCN || e->pp.kind == TDA_PROP_AM);
@@ -647,7 +647,7 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
   // the chains and the proposal factor only changes at a period boundary, so they are drawn for a whole WINDOW of steps (up to the
   // boundary / SMAX) in one launch and the blocks walk through it -- 60 launches of 48 us became 3 of 160 at C5 + error model.
   // Same counters, so the same draws.  TINYDA_ML_PREDRAW=0: one launch per block.
-  static const bool predraw_ok = !(getenv("TINYDA_ML_PREDRAW") && atoi(getenv("TINYDA_ML_PREDRAW")) == 0);
+  static const bool predraw_ok = env_int("TINYDA_ML_PREDRAW", 1) != 0;
   const bool predraw = predraw_ok && e->aem && !e->ext_hier && !e->is_dreamz && !e->rep_steps && !ml_split;
   int64_t win_t0 = 0, win_n = 0;  // steps [win_t0, win_t0 + win_n) are in the increment / uniform buffers
   bool inc_ready = false;  // the block about to start already has its increments (the swap launch of the block before it)
@@ -972,7 +972,7 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
       // model cuts them at every base subchain: 5 states) leave their states where the level kernel recorded them and the
       // boundary -- or the end of the run -- folds the period in one launch, state by state in the same order (the same bits).
       // Device outputs: the rows are contiguous in the caller's buffer; host outputs: staged.  TINYDA_AM_DEFER=0: every block.
-      static const bool defer_ok = !(getenv("TINYDA_AM_DEFER") && atoi(getenv("TINYDA_AM_DEFER")) == 0);
+      static const bool defer_ok = env_int("TINYDA_AM_DEFER", 1) != 0;
       const bool last_block = done_base + S >= total_base;
       const double* fold_rows = ma.rec_params[0];
       int64_t fold_n = S, fold_t0 = e->t;
@@ -1148,7 +1148,7 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
           ScopedTimer tm(e, 3);
           // the model outputs the decision and the update need, for all chains on the matrix cores (TINYDA_AEM_PRE=0: matrix-vector
           // products per chain inside k_aem_action)
-          static const bool pre_ok = !(getenv("TINYDA_AEM_PRE") && atoi(getenv("TINYDA_AEM_PRE")) == 0);
+          static const bool pre_ok = env_int("TINYDA_AEM_PRE", 1) != 0;
           if (pre_ok && e->aem_F.p && e->levels[qq].Apk.p && e->levels[qq - 1].Apk.p) {
             LinMultiArgs la{};
             la.N = N;

@@ -166,8 +166,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
   // Philox mode: the normals and uniforms of a block do not depend on the chains, so block b+1's are drawn on a second
   // stream while block b's k_mh_steps runs (k_rng fits into the registers the step kernel leaves free); only
   // INC = Z L^T (k_apply) stays on the critical path behind the Cholesky swap.  Replay mode keeps the fused k_propose.
-  static const bool split_ok = !(getenv("TINYDA_SPLIT_PROPOSE") && atoi(getenv("TINYDA_SPLIT_PROPOSE")) == 0);
-  const bool split = split_ok && !e->rep_steps;
+  const bool split = !e->rep_steps;
   if (split && !e->rng_stream) {
     HIP_TRY(hipStreamCreateWithFlags(&e->rng_stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
@@ -401,7 +400,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       aa.acc_count = e->acc_count.p;
       aa.flags = e->flags.p;
       ScopedTimer tm(e, 2);
-      static const bool fuse_ok = !(getenv("TINYDA_FUSE_CHOL_APPLY") && atoi(getenv("TINYDA_FUSE_CHOL_APPLY")) == 0);  // A/B switch
+      static const bool fuse_ok = env_int("TINYDA_FUSE_CHOL_APPLY", 1) != 0;  // A/B switch
       CholArgs ca{};
       ca.N = N;
       ca.d = d;

@@ -1300,13 +1300,7 @@ __device__ __forceinline__ double bcast_lane64(double v, int src) {
 // dominate there), at DPAD = 32 nothing (150 us: four resident waves x 125 instructions, the vector unit 56 % busy); not
 // adopted, no benchmark configuration adapts in fewer than 64 dimensions.
 // the moment recursion of one chain by its wave; Sigma is left in Sg (and stored): k_adapt, and the first half of k_adapt_chol_apply
-// HALF: -1 = every tile row; 0 / 1 (64 parameters, k_adapt_split): the tile rows {0, 3} / {1, 2} -- five of the ten tiles each -- for two
-// waves that share a chain: 80 instead of 160 registers of Sigma and t mu mu^T, four waves per SIMD instead of two
-template <int HALF>
-__host__ __device__ constexpr bool am_row_mine(int ti) {
-  return HALF < 0 || (HALF == 0 ? (ti == 0 || ti == 3) : (ti == 1 || ti == 2));
-}
-template <int DPAD, int HALF = -1>
+template <int DPAD>
 __device__ __forceinline__ void adapt_am_chain(const AdaptArgs& a, const int64_t c, const int lane, double (&Sg)[am_tiles<DPAD>()][4]) {
   constexpr int T = am_tile_rows<DPAD>();
   constexpr int NTL = am_tiles<DPAD>();
@@ -1325,7 +1319,7 @@ __device__ __forceinline__ void adapt_am_chain(const AdaptArgs& a, const int64_t
       for (int tj = 0; tj <= ti; ++tj)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (am_row_mine<HALF>(ti)) Sg[ti * (ti + 1) / 2 + tj][r] = sig[((ti * (ti + 1) / 2 + tj) * 4 + r) * 64 + lane];
+          Sg[ti * (ti + 1) / 2 + tj][r] = sig[((ti * (ti + 1) / 2 + tj) * 4 + r) * 64 + lane];
     double mu = lp ? a.am_mu[c * DPAD + lane] : 0.0;
     const int ppos = (lane & ~15) | ((lane & 3) << 2) | ((lane >> 2) & 3);
     // (t + 1) (mu'_s mu'_s^T) of step s IS t (mu_{s+1} mu_{s+1}^T) of step s + 1 (same operands, same rounding): it is
@@ -1341,7 +1335,6 @@ __device__ __forceinline__ void adapt_am_chain(const AdaptArgs& a, const int64_t
       for (int tj = 0; tj < T; ++tj) mc[tj] = s_nat[16 * tj + lc];
 #pragma unroll
       for (int ti = 0; ti < T; ++ti) {
-        if (!am_row_mine<HALF>(ti)) continue;
         const double2* __restrict__ q = reinterpret_cast<const double2*>(s_prm + 16 * ti + 4 * hi);
         const double2 m01 = q[0], m23 = q[1];
         const double mr[4] = {m01.x, m01.y, m23.x, m23.y};
@@ -1389,7 +1382,6 @@ __device__ __forceinline__ void adapt_am_chain(const AdaptArgs& a, const int64_t
       }
 #pragma unroll
       for (int ti = 0; ti < T; ++ti) {
-        if (!am_row_mine<HALF>(ti)) continue;
         double xr[4], pr[4];
         {
           const double2* __restrict__ q = reinterpret_cast<const double2*>(s_prm + 16 * ti + 4 * hi);
@@ -1412,14 +1404,14 @@ __device__ __forceinline__ void adapt_am_chain(const AdaptArgs& a, const int64_t
       }
       mu = mup;
     }
-    if (lp && HALF <= 0) a.am_mu[c * DPAD + lane] = mu;  // (both halves carry the mean; one stores it)
+    if (lp) a.am_mu[c * DPAD + lane] = mu;
 #pragma unroll
     for (int ti = 0; ti < T; ++ti)
 #pragma unroll
       for (int tj = 0; tj <= ti; ++tj)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (am_row_mine<HALF>(ti)) sig[((ti * (ti + 1) / 2 + tj) * 4 + r) * 64 + lane] = Sg[ti * (ti + 1) / 2 + tj][r];
+          sig[((ti * (ti + 1) / 2 + tj) * 4 + r) * 64 + lane] = Sg[ti * (ti + 1) / 2 + tj][r];
   }
 }
 
@@ -1433,16 +1425,9 @@ __device__ __forceinline__ void adapt_am_chain(const AdaptArgs& a, const int64_t
 // of Sigma unchanged; same operations per element in the same order: the same bits (the "+ 0" that the tile version adds to the
 // off-diagonal elements of a diagonal tile is not added: it can change the sign of a zero only).  NEED_TILES: leave the diagonal
 // tiles in Sg in the tile layout (k_adapt_chol_apply factorises from registers), converted through LDS once per block.
-#ifndef CIRC_SCHED
-#define CIRC_SCHED
-#endif
 // one ds_read_b64 (2 LDS cycles per wave: MI355X_MICROARCH.md, LDS), kept from being paired into a ds_read2_b64 (8 cycles)
 __device__ __forceinline__ double lds_b64(const double* p) {
-#ifdef CIRC_TIMING_NOLDS
-  return (double)(int)(size_t)p;  // timing-only build: no read
-#else
   return *(const volatile __attribute__((address_space(3))) double*)p;
-#endif
 }
 template <bool NEED_TILES>
 __device__ __forceinline__ void adapt_am_chain_c64_store(const AdaptArgs& a, const int64_t c, const int lane, const double mu, double (&Sg)[10][4],
@@ -1539,11 +1524,7 @@ __device__ __forceinline__ void adapt_am_chain_c64(const AdaptArgs& a, const int
 #pragma unroll
     for (int ti = 1; ti < 4; ++ti) {
       const double2* __restrict__ q = reinterpret_cast<const double2*>(s_prm + 16 * ti + 4 * hi);
-#ifdef CIRC_TIMING_NOLDS
-      const double2 x01 = {x, mup}, x23 = {mup, x}, p01 = {x + 1.0, mup}, p23 = {x, mup + 1.0};
-#else
       const double2 x01 = q[0], x23 = q[1], p01 = q[W / 2], p23 = q[W / 2 + 1];
-#endif
       xr[ti][0] = x01.x; xr[ti][1] = x01.y; xr[ti][2] = x23.x; xr[ti][3] = x23.y;
       pr[ti][0] = p01.x; pr[ti][1] = p01.y; pr[ti][2] = p23.x; pr[ti][3] = p23.y;
     }
@@ -1684,26 +1665,6 @@ __global__ void __launch_bounds__(64, CIRC ? 2 : 1) k_adapt(const AdaptArgs a) {
 }
 
 // AdaptiveMetropolis(block_moments=True): the covariance as one rank-S update per block (see above)
-// The same recursion with the ten tiles of a 64-parameter chain dealt to TWO waves (workgroups 2 c and 2 c + 1: tile rows {0, 3} and
-// {1, 2}), each carrying the mean itself: 5 tiles of Sigma and of t mu mu^T per wave, at most 128 registers, FOUR waves per SIMD.  The
-// loop is bound by vector issue (434 vector instructions per state); tools/valu_rate_probe.hip prices that mix at 3.95
-// cycles per instruction with two waves per SIMD and 2.87 with four.  Same operations per element, same results bit for bit.
-template <int DPAD>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_adapt_split(const AdaptArgs a) {
-  static_assert(DPAD == 64, "four tile rows");
-  const int lane = threadIdx.x;
-  const int64_t c = blockIdx.x >> 1;
-  if (c >= a.N) return;
-  if (blockIdx.x & 1) {
-    double Sg[am_tiles<DPAD>()][4];
-    adapt_am_chain<DPAD, 1>(a, c, lane, Sg);
-  } else {
-    double Sg[am_tiles<DPAD>()][4];
-    adapt_am_chain<DPAD, 0>(a, c, lane, Sg);
-    adapt_scaling(a, c, lane);
-  }
-}
-
 template <int DPAD>
 __global__ void __launch_bounds__(64) k_adapt_block(const AdaptArgs a) {
   constexpr int T = am_tile_rows<DPAD>();

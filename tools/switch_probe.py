@@ -1,6 +1,6 @@
 """One seeded run of a configuration whose kernel choice an environment switch changes; records to an .npz.  The switches are
 read once per process, so A/B comparisons start this script twice (tests/test_gpu_switches.py).
-    python tools/switch_probe.py {mlda3|mlda3_short|da2|aemd|aemd_lean|aem_dense|aem_dense_da_pcn|aem_dense_m200|aem_dense_chunks|dream|am}[_ragged] out.npz     (_ragged: a chain count that is not a multiple of the 16-chain tile)"""
+    python tools/switch_probe.py {mlda3|mlda3_short|da2|aemd|aemd_lean|aem_dense|aem_dense_da_pcn|aem_dense_m200|aem_dense_chunks|dream|am|am_d24}[_ragged] out.npz     (_ragged: a chain count that is not a multiple of the 16-chain tile)"""
 import os
 import sys
 
@@ -48,20 +48,26 @@ def dream(N=512, d=32, T=70, M0=64, K=16):
     return dict(params0=P, stats0=S, acc0=A, pCR=st["pCR"])
 
 
-def single_am(N=96, d=64, m=200, T=330):
-    """single-level AdaptiveMetropolis over several covariance swaps (k_chol_apply against k_chol + k_apply)"""
+def single_am(N=96, d=64, m=200, T=330, period=60):
+    """single-level AdaptiveMetropolis over several covariance swaps (k_chol_apply against k_chol + k_apply); the run is cut at
+    the last swap, whose Sigma (sigma_swap) is the matrix the final factor C = L L^T comes from"""
     rng = np.random.default_rng(12)
     A = rng.standard_normal((m, d)) / 8
     truth = rng.standard_normal(d)
     e = engine.Engine(N, d, seed=10)
     e.set_prior(np.zeros(d), np.eye(d))
     e.set_level(0, A, A @ truth + 0.1 * rng.standard_normal(m), 0, 0.01)
-    e.set_proposal(2, 1e-4 * np.eye(d), t0=60, period=60, adaptive=True)
+    e.set_proposal(2, 1e-4 * np.eye(d), t0=period, period=period, adaptive=True)
     e.init(truth + 0.05 * rng.standard_normal((N, d)))
-    P, S, Acc = e.run_host(T)
+    t_swap = T // period * period
+    runs = [e.run_host(t_swap)]
+    sigma_swap = e.proposal_state(want_am=True)["am_sigma"]
+    if T > t_swap:
+        runs.append(e.run_host(T - t_swap))
+    P, S, Acc = (np.concatenate(r) for r in zip(*runs))
     st = e.proposal_state(want_am=True)
     e.close()
-    return dict(params0=P, stats0=S, acc0=Acc, C=st["C"], sigma=st["am_sigma"], scaling=st["scaling"])
+    return dict(params0=P, stats0=S, acc0=Acc, C=st["C"], sigma=st["am_sigma"], sigma_swap=sigma_swap, scaling=st["scaling"])
 
 
 if __name__ == "__main__":
@@ -94,6 +100,8 @@ if __name__ == "__main__":
         res = single_am(N=96 - cut)
     elif what in ("am_d40", "am_d33"):  # fewer than 64 parameters on the 64-parameter instances: padded rows / columns of Sigma
         res = single_am(N=96 - cut, d=int(what[4:]), m=120, T=250)
+    elif what == "am_d24":  # the 32-parameter instances: the row-per-lane factorisation k_chol / k_chol_apply
+        res = single_am(N=96 - cut, d=24, m=120)
     else:
         res = dream(N=512 - cut)
     np.savez(out, **res)
