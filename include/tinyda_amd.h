@@ -185,7 +185,7 @@ const char* tda_last_error(void);
  * tda_engine_set_progress / get_progress, tda_engine_detach_proposal_state + tda_proposal_snapshot_*,
  * tda_engine_set_proposal_spectrum; 0.4 tda_profile grew n_launch_aem / ms_aem (struct_size 48 is still accepted), checkpoint blobs
  * carry the ABI / RNG-contract version and older blobs are refused; 0.5 no entry point added or changed: tda_config.dim up to 128
- * (single-level chains and two-level hierarchies, see tda_config), the dense error model kept as the Cholesky factor instead of its triangular inverse (same
+ * (single-level chains and hierarchies of two to four levels, see tda_config), the dense error model kept as the Cholesky factor instead of its triangular inverse (same
  * results through tda_engine_get_error_model; checkpoint blobs are format 4 -- six levels' counters -- and older blobs are refused). */
 const char* tda_version(void);
 

@@ -57,6 +57,20 @@ def test_draws_on_the_second_stream_change_nothing(what, tmp_path):
         assert np.array_equal(on[k], plain[k]), "%s differs between the two entry points (%s)" % (k, what)
 
 
+@pytest.mark.parametrize("what", ["da2_wide_am", "da2_wide_grw"])
+def test_draws_on_the_second_stream_change_nothing_above_64_parameters(what, tmp_path):
+    """96 parameters: TINYDA_ML_SPLIT=1 (the draws of block b + 1 under block b, the increments of the factor tiles by k_wide_apply
+    at the head of the block or, at an AdaptiveMetropolis swap, behind the factorisation) against TINYDA_ML_SPLIT=0 (k_propose's
+    128-parameter form in front of every block): the same normals through the same product"""
+    on, off = _probe(what, {"TINYDA_ML_SPLIT": "1"}, tmp_path, "split"), _probe(what, {"TINYDA_ML_SPLIT": "0"}, tmp_path, "one_stream")
+    for k in on:
+        if k.startswith("acc"):
+            assert np.array_equal(on[k], off[k]), "%s differs (%s)" % (k, what)
+        else:
+            np.testing.assert_allclose(on[k], off[k], rtol=1e-10, atol=1e-12, err_msg=k)
+    assert 0.02 < on["acc0"].mean() < 0.98
+
+
 def _host_factor(C):
     """the lower Cholesky factor of every chain's matrix, on the host"""
     return np.stack([np.linalg.cholesky(c) for c in C])

@@ -647,3 +647,177 @@ def test_wide_hierarchy_with_error_model_over_external_models(case):
         if i == nl - 1:
             np.testing.assert_allclose(outs[i][1][:, :, 2], (np.asarray(ref["logprior"]) + np.asarray(ref["loglike"]))[:, sk].T, rtol=1e-10)
     assert 0.0 < outs[nl - 1][2].mean() <= 1.0 and np.all(np.isfinite(bias)) and np.all(np.isfinite(P))
+
+
+# ---- tda_engine_set_proposal_covariance, checkpoints of a shared factor, refusals: narrow and 65 .. 128 parameters ----
+
+def _grw_engine(d, N, A, y, nz, theta0, C0, seed, n_levels=1, As=None, ys=None, sl=None):
+    from tinyda_amd.engine import Engine
+
+    e = Engine(N, d, seed=seed, n_levels=n_levels)
+    e.set_prior(np.zeros(d), np.eye(d))
+    if n_levels == 1:
+        e.set_level(0, A, y, 0, nz)
+    else:
+        for k in range(n_levels):
+            e.set_level(k, As[k], ys[k], 0, 0.01)
+        e.set_subchains(sl)
+    e.set_proposal(0, C0, scaling=0.8)
+    e.init(theta0)
+    return e
+
+
+@pytest.mark.parametrize("when", ["after_init", "between_runs"])
+@pytest.mark.parametrize("d", [16, 64, 65, 96, 128])
+def test_set_proposal_covariance_against_the_oracle(d, when):
+    """a covariance set on a GaussianRandomWalk engine (the shared factor: dense below 65 parameters, tiles above) is the one the
+    engine reads back and the one its steps use: replayed through the oracle, segment by segment, accept masks bit for bit"""
+    N, m, T = 16, 30, 40
+    rng, A, y, theta0, nz = _problem(d, m, N, 2000 + d)
+    C0, C = _spd(rng, d, 4e-3 / d), _spd(rng, d, 8e-3 / d)
+    e = _grw_engine(d, N, A, y, nz, theta0, C0, seed=55 + d)
+    z, u = e.set_export(T)
+    k = 0 if when == "after_init" else 13
+    first = e.run_host(k) if k else None
+    e.set_proposal_covariance(C)
+    Cr = e.proposal_state()["C"]
+    rest = e.run_host(T - k)
+    e.close()
+    assert Cr.shape == (N, d, d)
+    for c in range(N):
+        np.testing.assert_allclose(Cr[c], C, rtol=1e-12, atol=1e-13 * np.abs(C).max(), err_msg="chain %d" % c)
+    lvl = orc.LinearGaussianLevel(A, y, "iso", nz, orc.MVNPrior(np.zeros(d), np.eye(d)))
+    segs = ([(slice(0, k), C0, theta0, first)] if k else []) + [(slice(k, T), C, first[0][-1] if k else theta0, rest)]
+    for sl, Cs, start, (params, stats, acc) in segs:
+        res = orc.run_mh(lvl, dict(kind="grw", C=Cs, scaling=0.8), start, np.swapaxes(z[sl], 0, 1), np.swapaxes(u[sl], 0, 1))
+        ref_acc = np.swapaxes(res["accepted"][:, 1:], 0, 1)
+        assert np.array_equal(acc, ref_acc), "steps %s: %d accept flips" % (sl, int((acc != ref_acc).sum()))
+        np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(res["logpost"][:, 1:], 0, 1), rtol=1e-10)
+    assert 0.02 < rest[2].mean() < 0.98
+
+
+def test_set_proposal_covariance_delayed_acceptance_at_96_parameters():
+    """the covariance set after init on a two-level Delayed Acceptance GaussianRandomWalk engine at 96 parameters, against the
+    multilevel oracle: accept masks of both levels bit for bit, log-posteriors to 1e-10"""
+    from tests.test_gpu_multilevel import _oracle_uniforms
+
+    d, ms, L, N, n_fine = 96, (24, 70), 3, 17, 10
+    rng = np.random.default_rng(7300 + d)
+    truth = 0.5 * rng.standard_normal(d)
+    As = [rng.standard_normal((m, d)) / np.sqrt(d) for m in ms]
+    ys = [A @ truth + 0.1 * rng.standard_normal(len(A)) for A in As]
+    theta0 = truth + 0.05 * rng.standard_normal((N, d))
+    C = _spd(rng, d, 4e-3 / d)
+    seed = 950 + d
+    e = _grw_engine(d, N, None, None, None, theta0, np.eye(d), seed, n_levels=2, As=As, ys=ys, sl=[L])
+    e.set_proposal_covariance(C)
+    rows = e.rows_per_level(n_fine)
+    z, _ = e.set_export(rows[0])
+    outs = e.run_levels_host(n_fine)
+    e.close()
+    us, ridx = _oracle_uniforms(seed, N, rows, [L], None)
+    prior = orc.MVNPrior(np.zeros(d), np.eye(d))
+    levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.01, prior) for k in range(2)]
+    res, _ = orc.run_multilevel(levels, dict(kind="grw", C=C, scaling=0.8), [L], theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
+    for k in range(2):
+        sk = slice(1, None) if k == 1 else slice(None)
+        assert np.array_equal(outs[k][2], res[k]["accepted"][:, sk].T), "level %d accept masks differ" % k
+        np.testing.assert_allclose(outs[k][1][:, :, 2], res[k]["logpost"][:, sk].T, rtol=1e-10)
+    assert 0.0 < outs[0][2].mean() < 1.0
+
+
+@pytest.mark.parametrize("case", ["da96_identity", "da96_set_cov", "single128_set_cov"])
+def test_wide_shared_factor_checkpoint_resume_is_bitwise(case):
+    """get_state / set_state of a shared GaussianRandomWalk factor above 64 parameters: the identity (increments = the normals,
+    k_rng_direct) and a covariance set at run time (the factor tiles); a run interrupted mid-way and resumed in a fresh engine that
+    was initialised with the identity continues bit for bit, with the saved covariance"""
+    d, N = (128, 16) if case.startswith("single") else (96, 17)
+    rng = np.random.default_rng(8100 + d)
+    truth = 0.5 * rng.standard_normal(d)
+    As = [rng.standard_normal((m, d)) / np.sqrt(d) for m in (24, 70)]
+    ys = [A @ truth + 0.1 * rng.standard_normal(len(A)) for A in As]
+    theta0 = truth + 0.05 * rng.standard_normal((N, d))
+    C = _spd(rng, d, 4e-3 / d)
+    if case.startswith("single"):
+        make = lambda: _grw_engine(d, N, As[1], ys[1], 0.01, theta0, np.eye(d), seed=61)
+        run = lambda e, n: list(e.run_host(n))
+        n1, n2 = 23, 31
+    else:
+        make = lambda: _grw_engine(d, N, None, None, None, theta0, np.eye(d), seed=62, n_levels=2, As=As, ys=ys, sl=[3])
+        run = lambda e, n: [a for lvl in e.run_levels_host(n) for a in lvl]
+        n1, n2 = 5, 7
+
+    def started():
+        e = make()
+        if case.endswith("set_cov"):
+            e.set_proposal_covariance(C)
+        return e
+
+    a = started()
+    full_1, full_2 = run(a, n1), run(a, n2)
+    a.close()
+    b = started()
+    first = run(b, n1)
+    blob = b.get_state()
+    C_saved = b.proposal_state()["C"]
+    b.close()
+    c = make()
+    c.set_state(blob)
+    C_restored = c.proposal_state()["C"]
+    rest = run(c, n2)
+    c.close()
+    for x, y in zip(first, full_1):
+        assert np.array_equal(x, y)
+    for i, (x, y) in enumerate(zip(rest, full_2)):
+        assert np.array_equal(x, y), "record %d differs after the restore" % i
+    assert np.array_equal(C_restored, C_saved)
+    if case.endswith("set_cov"):
+        np.testing.assert_allclose(C_saved[0], C, rtol=1e-12, atol=1e-13 * np.abs(C).max())
+
+
+def test_entry_points_that_do_not_serve_wide_engines_refuse():
+    """what has no 65 .. 128-parameter instance refuses with TDA_ERR_UNSUPPORTED instead of returning numbers: rng_probe on an
+    initialised engine; DREAM(Z), the diagonal error model in a hierarchy and more than four levels at set-up"""
+    from tinyda_amd._lib import EngineError
+    from tinyda_amd.engine import Engine
+
+    d, N = 96, 16
+    rng = np.random.default_rng(5)
+    A, y = rng.standard_normal((20, d)) / np.sqrt(d), rng.standard_normal(20)
+    theta0 = 0.1 * rng.standard_normal((N, d))
+    e = _grw_engine(d, N, A, y, 0.01, theta0, np.eye(d), seed=3)
+    try:
+        with pytest.raises(EngineError, match="rng_probe is not lowered for more than 64 parameters"):
+            e.rng_probe(0)
+    finally:
+        e.close()
+
+    def dreamz(e):
+        e.set_level(0, A, y, 0, 0.01)
+        e.set_proposal_dreamz(32, delta=1, nCR=3, capacity=32 + 8 * N)
+        e.set_archive(None)
+        e.init(None)
+
+    def diag_error_model(e):
+        for k in range(2):
+            e.set_level(k, A, y, 0, 0.01)
+        e.set_proposal(1, None, scaling=0.02)
+        e.set_subchains([3])
+        e.set_error_model("state-independent-diagonal")
+        e.init(theta0)
+
+    def five_levels(e):
+        for k in range(5):
+            e.set_level(k, A, y, 0, 0.01)
+        e.set_proposal(1, None, scaling=0.02)
+        e.set_subchains([2, 2, 2, 2])
+        e.init(theta0)
+
+    for configure, nl in ((dreamz, 1), (diag_error_model, 2), (five_levels, 5)):
+        e = None
+        with pytest.raises(EngineError, match="more than 64 parameters"):
+            e = Engine(N, d, seed=3, n_levels=nl)
+            e.set_prior(np.zeros(d), np.eye(d))
+            configure(e)
+        if e is not None:
+            e.close()

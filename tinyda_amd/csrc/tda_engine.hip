@@ -131,6 +131,28 @@ void factor_form_unpack_host(const double* w, int m, std::vector<double>& L) {
     for (int j = 0; j < (i & ~15); ++j) L[(size_t)i * m + j] = w[tda::aemr_w_offset_offdiag(i, j)];
 }
 
+// 65 .. 128 parameters (tda_kernels_wide.h): one factor buffer of a d x d lower Cholesky factor L (row-major) -- U = L^T off the
+// diagonal in the factor form's order (fac: WIDE_FACTOR_DOUBLES) and the diagonal tiles U_pp beside them (ud: WIDE_UD_DOUBLES),
+// identity in the padding.  What tda_engine_init and tda_engine_set_proposal_covariance upload, and wide_factor_unpack_host reads.
+void wide_factor_pack_host(const std::vector<double>& L, int d, std::vector<double>& fac, std::vector<double>& ud) {
+  factor_form_pack_host(L, d, 128, fac);
+  ud.assign(tda::WIDE_UD_DOUBLES, 0.0);
+  for (int p = 0; p < tda::WIDE_T; ++p)
+    for (int k = 0; k < 16; ++k)
+      for (int j = k; j < 16; ++j) {
+        const int gi = 16 * p + j, gk = 16 * p + k;  // U_pp[k][j] = L[16 p + j][16 p + k]; padding: identity
+        ud[(size_t)(p * 4 + (k >> 2)) * 64 + (k & 3) * 16 + j] = (gi < d && gk < d) ? L[(size_t)gi * d + gk] : (gi == gk ? 1.0 : 0.0);
+      }
+}
+// ... and back: L (d x d, row-major) from one factor buffer's tiles
+void wide_factor_unpack_host(const double* f, const double* u, int d, std::vector<double>& L) {
+  L.assign((size_t)d * d, 0.0);
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j <= i; ++j)
+      L[(size_t)i * d + j] = (i >> 4) == (j >> 4) ? u[(size_t)((i >> 4) * 4 + ((j & 15) >> 2)) * 64 + (j & 3) * 16 + (i & 15)]  // U_pp[j][i]
+                                                  : f[tda::aemr_w_offset_offdiag(i, j)];
+}
+
 // pack an (rows x cols) row-major matrix into MFMA A-operand fragments, see LevelDev::Apk; kpad = padded K
 void pack_fragments(const double* A, int rows, int cols, int dpad, std::vector<double>& out, int& ncb) {
   ncb = (rows + 15) / 16;
@@ -497,8 +519,9 @@ void launch_steps(const StepArgs& a, int64_t tiles, size_t lds, hipStream_t st) 
   }
 }
 template <int DPAD>
-void launch_propose(const ProposeArgs& a, hipStream_t st) {
+int launch_propose(const ProposeArgs& a, hipStream_t st) {  // (propose / apply / chol_apply return a status: see launch_apply<128>)
   hipLaunchKernelGGL(k_propose<DPAD>, dim3((unsigned)a.NP), dim3(64), 0, st, a);
+  return TDA_OK;
 }
 template <int DPAD>
 void launch_rng_direct(const RngArgs& a, double* inc, hipStream_t st) {
@@ -512,8 +535,9 @@ void launch_rng(const RngArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_rng<DPAD>, dim3((unsigned)a.NP, (unsigned)((a.S + 15) / 16)), dim3(64), 0, st, a);
 }
 template <int DPAD>
-void launch_apply(const ApplyArgs& a, hipStream_t st) {
+int launch_apply(const ApplyArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_apply<DPAD>, dim3((unsigned)a.NP), dim3(64), 0, st, a);
+  return TDA_OK;
 }
 // TINYDA_ADAPT_CIRC=0 reaches the tile-form recursion at 64 parameters only through this switch; it stays as the bitwise comparator
 // of the circulant one (tests/test_gpu_switches.py)
@@ -538,12 +562,13 @@ void launch_chol(const CholArgs& a, hipStream_t st) {
   }
 }
 template <int DPAD>
-void launch_chol_apply(const CholArgs& a, const ApplyArgs& ap, hipStream_t st) {
+int launch_chol_apply(const CholArgs& a, const ApplyArgs& ap, hipStream_t st) {
   if constexpr (DPAD == 64) {  // four 16-column panels: the blocked kernel
     hipLaunchKernelGGL(k_chol_apply_blk<DPAD>, dim3((unsigned)ap.NP), dim3(64), 0, st, a, ap);
   } else {
     hipLaunchKernelGGL(k_chol_apply<DPAD>, dim3((unsigned)ap.NP), dim3(64), 0, st, a, ap);
   }
+  return TDA_OK;
 }
 
 // the period boundary of the single-level AdaptiveMetropolis pipeline in one launch (k_adapt_chol_apply, DPAD = 64 only)
@@ -580,14 +605,22 @@ static WideApplyArgs wide_apply_args(const ApplyArgs& a) {
   w.inc = a.inc;
   return w;
 }
+// (every ApplyArgs of a 128-parameter engine goes through wide_fill: a site that misses it is an error here, not a launch over null
+// tile pointers; launch_adapt_chol_apply never launches at 128 parameters, its callers fall back to launch_chol_apply)
+static int wide_apply_refused(const ApplyArgs& a, bool per_chain) {
+  if (a.Lk && a.ud && (a.sel || !per_chain)) return TDA_OK;
+  return fail(TDA_ERR_STATE, "internal: a 128-parameter apply without its factor tiles (%s missing)", !a.Lk ? "factor" : !a.ud ? "diagonal tiles" : "buffer selector");
+}
 template <>
-void launch_apply<128>(const ApplyArgs& a, hipStream_t st) {
+int launch_apply<128>(const ApplyArgs& a, hipStream_t st) {
+  if (int rc = wide_apply_refused(a, a.L_stride != 0)) return rc;
   hipLaunchKernelGGL(k_wide_apply<WIDE_T>, dim3((unsigned)a.NP), dim3(64), 0, st, wide_apply_args(a));
+  return TDA_OK;
 }
 // the fused proposal (replay mode, the hierarchies' per-block draws): uniforms, the normals as fragments (recorded ones converted,
 // or k_rng<128>), the product
 template <>
-void launch_propose<128>(const ProposeArgs& a, hipStream_t st) {
+int launch_propose<128>(const ProposeArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_wide_uniforms, dim3((unsigned)(((int64_t)a.S * a.NP + 255) / 256)), dim3(256), 0, st, a);
   const dim3 g((unsigned)a.NP, (unsigned)((a.S + 15) / 16));
   if (a.z_replay) {
@@ -622,7 +655,7 @@ void launch_propose<128>(const ProposeArgs& a, hipStream_t st) {
   ap.ud = a.ud;
   ap.sel = a.sel;
   ap.NPf = a.NPf;
-  launch_apply<128>(ap, st);
+  return launch_apply<128>(ap, st);
 }
 template <>
 void launch_adapt<128>(const AdaptArgs& a, hipStream_t st) {
@@ -647,9 +680,10 @@ void launch_chol<128>(const CholArgs& a, hipStream_t st) {  // C <- Sigma: the e
   hipLaunchKernelGGL((k_aem_refresh<WIDE_T, 1>), dim3((unsigned)a.N), dim3(64), 0, st, ra);
 }
 template <>
-void launch_chol_apply<128>(const CholArgs& a, const ApplyArgs& ap, hipStream_t st) {
+int launch_chol_apply<128>(const CholArgs& a, const ApplyArgs& ap, hipStream_t st) {
+  if (int rc = wide_apply_refused(ap, true)) return rc;  // (a covariance swap: per-chain factors)
   launch_chol<128>(a, st);
-  launch_apply<128>(ap, st);
+  return launch_apply<128>(ap, st);
 }
 
 // k_aem_refresh<T, NSUM> for the engine's row stride (64 / 128 -> 4 / 8 tile rows; 256: k_aem_refresh_big<16, NSUM>) and the number of trackers summed
@@ -854,15 +888,21 @@ void launch_dz_adapt(const DreamAdaptArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_dreamz_adapt<DPAD>, dim3((unsigned)a.N), dim3(64), 0, st, a);
 }
 
+// the sites that serve 1 .. 64 parameters only.  A 128-parameter engine never reaches one: the DREAM(Z) sites are refused for it
+// at tda_engine_init, the diagonal error model in a hierarchy too (the fused base subchains of run_ext_hierarchy_block), and
+// tda_engine_rng_probe refuses it; should one be reached all the same, the call fails instead of running a 64-parameter instance
+// over 128-parameter buffers.  (Every site is in a function that returns a TDA_ status.)
 #define DISPATCH_DPAD(dp, CALL)                  \
   switch (dp) {                                  \
     case 8: { constexpr int DPAD = 8; CALL; } break;   \
     case 16: { constexpr int DPAD = 16; CALL; } break; \
     case 32: { constexpr int DPAD = 32; CALL; } break; \
-    default: { constexpr int DPAD = 64; CALL; } break; \
+    case 64: { constexpr int DPAD = 64; CALL; } break; \
+    default: return fail(TDA_ERR_UNSUPPORTED, "no kernel instance for a row stride of %d parameters at this site", (int)(dp)); \
   }
 
-// the single-level sites (run_single, evaluate): 65 .. 128 parameters too (launch_*<128>: tda_kernels_wide.h)
+// the single-level sites (run_single, evaluate): 65 .. 128 parameters too (launch_*<128>: tda_kernels_wide.h); dpad_for gives no
+// other row stride, so the default is 64
 #define DISPATCH_DPAD_W(dp, CALL)                    \
   switch (dp) {                                      \
     case 8: { constexpr int DPAD = 8; CALL; } break;     \

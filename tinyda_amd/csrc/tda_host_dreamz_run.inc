@@ -157,7 +157,7 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     if (e->dz.M0 + (e->dist_steps + e->dist_pending + n_iter) * N > e->arch_cap) return fail(TDA_ERR_INVALID, "archive segment capacity (%lld rows) exceeded", (long long)e->arch_cap);
   }
   // everything DREAMZ.make_proposal draws for the S steps of the next block
-  auto enqueue_draw = [&](int64_t S, bool gather, const DreamFuseArgs* fuse = nullptr) {
+  auto enqueue_draw = [&](int64_t S, bool gather, const DreamFuseArgs* fuse = nullptr) -> int {
     DreamDrawArgs da{};
     da.N = N;
     da.NP = NP;
@@ -203,6 +203,7 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       da.seg = e->dist_seg_dev.p;
     }
     DISPATCH_DPAD(DP, launch_dz_draw<DPAD>(da, e->stream, fuse));
+    return TDA_OK;
   };
   int64_t done = 0;
   while (done < n_iter) {
@@ -217,7 +218,7 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
                        lv.model == MODEL_ROSENBROCK && e->prior_kind != PRIOR_DENSE && !e->rp_steps;
     if (!fused) {
       ScopedTimer tm(e, 0);
-      enqueue_draw(S, sh);
+      if (int rc = enqueue_draw(S, sh)) return rc;
     }
     sa.S = (int)S;
     sa.jump_ready = sh ? 1 : 0;
@@ -301,7 +302,7 @@ static int run_dreamz(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       fa.rec_acc = sa.rec_acc;
       fa.blk_states = sa.blk_states;
       ScopedTimer tm(e, 1);
-      enqueue_draw(S, true, &fa);
+      if (int rc = enqueue_draw(S, true, &fa)) return rc;
     } else {
       ScopedTimer tm(e, 1);
       DISPATCH_DPAD(DP, launch_dz_steps<DPAD>(sa, lds, e->stream));

@@ -309,14 +309,8 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     // 65 .. 128 parameters (tda_kernels_wide.h): the factor as tiles -- U = L^T off the diagonal in the factor form's order, the
     // diagonal tiles U_pp beside them -- in TWO buffers per chain (AdaptiveMetropolis: the swap writes the one that is not current)
     // or one shared set; the padding "Sigma_e" of the swap's factorisation
-    std::vector<double> fac, ud(WIDE_UD_DOUBLES, 0.0);
-    factor_form_pack_host(L, d, 128, fac);
-    for (int p = 0; p < WIDE_T; ++p)
-      for (int k = 0; k < 16; ++k)
-        for (int j = k; j < 16; ++j) {
-          const int gi = 16 * p + j, gk = 16 * p + k;  // U_pp[k][j] = L[16 p + j][16 p + k]; padding: identity
-          ud[(size_t)(p * 4 + (k >> 2)) * 64 + (k & 3) * 16 + j] = (gi < d && gk < d) ? L[(size_t)gi * d + gk] : (gi == gk ? 1.0 : 0.0);
-        }
+    std::vector<double> fac, ud;
+    wide_factor_pack_host(L, d, fac, ud);
     const bool am = e->pp.kind == TDA_PROP_AM;
     e->L_shared = !am;
     const int64_t NPf = am ? NP : 1;

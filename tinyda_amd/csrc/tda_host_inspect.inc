@@ -29,16 +29,12 @@ int read_proposal_view(const PropView& v, double* scaling, double* C, double* am
     HIP_TRY(hipMemcpy(hu.data(), v.ud, hu.size() * sizeof(double), hipMemcpyDeviceToHost));
     if (!v.L_shared) HIP_TRY(hipMemcpy(hs.data(), v.sel, NP * sizeof(int32_t), hipMemcpyDeviceToHost));
     auto unpack = [&](int64_t c0, int64_t c1) {
-      std::vector<double> L((size_t)d * d);
+      std::vector<double> L;
       for (int64_t c = c0; c < c1; ++c) {
         const int64_t cf = v.L_shared ? 0 : c;
         const double* f = hf.data() + ((size_t)hs[cf] * nL + cf) * tda::WIDE_FACTOR_DOUBLES;
         const double* u = hu.data() + ((size_t)hs[cf] * nL + cf) * tda::WIDE_UD_DOUBLES;
-        std::fill(L.begin(), L.end(), 0.0);
-        for (int i = 0; i < d; ++i)
-          for (int j = 0; j <= i; ++j)
-            L[(size_t)i * d + j] = (i >> 4) == (j >> 4) ? u[(size_t)((i >> 4) * 4 + ((j & 15) >> 2)) * 64 + (j & 3) * 16 + (i & 15)]  // U_pp[j][i]
-                                                        : f[tda::aemr_w_offset_offdiag(i, j)];
+        wide_factor_unpack_host(f, u, d, L);
         double* Cc = C + (size_t)c * d * d;
         for (int i = 0; i < d; ++i)
           for (int j = 0; j <= i; ++j) {
@@ -280,7 +276,9 @@ int tda_engine_rng_probe(tda_engine* e, int64_t step, double* z, double* u) {
   pa.u = ub.p;
   pa.z_export = zd.p;
   pa.u_export = ud.p;
-  DISPATCH_DPAD(DP, launch_propose<DPAD>(pa, e->stream));
+  int prc = TDA_OK;
+  DISPATCH_DPAD(DP, prc = launch_propose<DPAD>(pa, e->stream));
+  if (prc) return prc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(z, zd.p, (size_t)N * d * sizeof(double), hipMemcpyDeviceToHost));

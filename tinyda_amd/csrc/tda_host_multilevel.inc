@@ -716,8 +716,11 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
         ap.L_stride = pa.L_stride;
         ap.zf = e->zfrag[b].p;
         ap.inc = e->inc.p;
+        wide_fill(e, ap);
         ScopedTimer tm(e, 0);
-        DISPATCH_DPAD_W(DP, launch_apply<DPAD>(ap, e->stream));
+        int arc = TDA_OK;
+        DISPATCH_DPAD_W(DP, arc = launch_apply<DPAD>(ap, e->stream));
+        if (arc) return arc;
       }
       inc_ready = false;
       HIP_TRY(hipEventRecord(e->ev_apply[b], e->stream));
@@ -798,7 +801,9 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
         pa.NPf = e->L_shared ? 1 : NP;
       }
       ScopedTimer tm(e, 0);
-      DISPATCH_DPAD_W(DP, launch_propose<DPAD>(pa, e->stream));
+      int prc = TDA_OK;
+      DISPATCH_DPAD_W(DP, prc = launch_propose<DPAD>(pa, e->stream));
+      if (prc) return prc;
     }
 
     if (predraw) {  // this block's place in the window
@@ -1052,6 +1057,7 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
         ap.L_stride = (int64_t)DP * DP;
         ap.zf = e->zfrag[nb].p;
         ap.inc = e->inc.p;
+        wide_fill(e, ap);
       }
       bool one_launch = false;
       if (swap_apply) DISPATCH_DPAD_W(DP, one_launch = launch_adapt_chol_apply<DPAD>(aa, ca, ap, e->stream));
@@ -1060,7 +1066,9 @@ static int run_multilevel(tda_engine* e, int64_t n_fine, const tda_outputs* outs
       } else {
         DISPATCH_DPAD_W(DP, launch_adapt<DPAD>(aa, e->stream));
         if (swap_apply) {
-          DISPATCH_DPAD_W(DP, launch_chol_apply<DPAD>(ca, ap, e->stream));
+          int arc = TDA_OK;
+          DISPATCH_DPAD_W(DP, arc = launch_chol_apply<DPAD>(ca, ap, e->stream));
+          if (arc) return arc;
           inc_ready = true;
         } else if (do_swap) {
           DISPATCH_DPAD_W(DP, launch_chol<DPAD>(ca, e->stream));

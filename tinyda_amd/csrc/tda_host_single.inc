@@ -239,7 +239,9 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
         ap.inc = e->inc.p;
         wide_fill(e, ap);
         ScopedTimer tm(e, 0);
-        DISPATCH_DPAD_W(e->DP, launch_apply<DPAD>(ap, e->stream));
+        int arc = TDA_OK;
+        DISPATCH_DPAD_W(e->DP, arc = launch_apply<DPAD>(ap, e->stream));
+        if (arc) return arc;
       }
       inc_ready = false;
       HIP_TRY(hipEventRecord(e->ev_apply[b], e->stream));
@@ -290,7 +292,9 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     }
     {
       ScopedTimer tm(e, 0);
-      DISPATCH_DPAD_W(e->DP, launch_propose<DPAD>(pa, e->stream));
+      int prc = TDA_OK;
+      DISPATCH_DPAD_W(e->DP, prc = launch_propose<DPAD>(pa, e->stream));
+      if (prc) return prc;
     }
     }
 
@@ -438,7 +442,9 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       } else {
         DISPATCH_DPAD_W(e->DP, launch_adapt<DPAD>(aa, e->stream));
         if (swap_apply) {
-          DISPATCH_DPAD_W(e->DP, launch_chol_apply<DPAD>(ca, ap, e->stream));
+          int arc = TDA_OK;
+          DISPATCH_DPAD_W(e->DP, arc = launch_chol_apply<DPAD>(ca, ap, e->stream));
+          if (arc) return arc;
           inc_ready = true;
         } else if (do_swap) {
           DISPATCH_DPAD_W(e->DP, launch_chol<DPAD>(ca, e->stream));

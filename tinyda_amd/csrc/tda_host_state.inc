@@ -16,8 +16,13 @@ int tda_engine_reduce_moments(tda_engine* e, const double* rows, int64_t n_rows,
   const size_t nout = 1 + d + (size_t)d * d;
   if (!odev && (rc = outd.alloc(nout))) return rc;
   double* o = odev ? out : outd.p;
-  DISPATCH_DPAD(DP, hipLaunchKernelGGL(k_moments_partial<DPAD>, dim3((unsigned)nb), dim3(64), 0, e->stream, rows, n_rows, d, partial.p));
-  DISPATCH_DPAD(DP, hipLaunchKernelGGL(k_moments_final<DPAD>, dim3((unsigned)(d + 1)), dim3(64), 0, e->stream, partial.p, nb, n_rows, d, o));
+  if (DP == 128) {  // (S[128] per lane would spill: each block accumulates 64 rows of sum x x^T, blockIdx.y picks which)
+    hipLaunchKernelGGL(k_moments_partial_w, dim3((unsigned)nb, 2), dim3(128), 0, e->stream, rows, n_rows, d, partial.p);
+    hipLaunchKernelGGL(k_moments_final_w, dim3((unsigned)(d + 1)), dim3(128), 0, e->stream, partial.p, nb, n_rows, d, o);
+  } else {
+    DISPATCH_DPAD(DP, hipLaunchKernelGGL(k_moments_partial<DPAD>, dim3((unsigned)nb), dim3(64), 0, e->stream, rows, n_rows, d, partial.p));
+    DISPATCH_DPAD(DP, hipLaunchKernelGGL(k_moments_final<DPAD>, dim3((unsigned)(d + 1)), dim3(64), 0, e->stream, partial.p, nb, n_rows, d, o));
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (!odev) HIP_TRY(hipMemcpy(out, outd.p, nout * sizeof(double), hipMemcpyDeviceToHost));
@@ -32,11 +37,18 @@ int tda_engine_set_proposal_covariance(tda_engine* e, const double* C) {
   const int d = e->d, DP = e->DP;
   std::vector<double> Ch(C, C + (size_t)d * d), L;
   if (!cholesky_host(Ch.data(), d, L)) return fail(TDA_ERR_NUMERIC, "proposal covariance is not positive definite");
-  std::vector<double> Lk((size_t)DP * DP, 0.0);
-  for (int j = 0; j < d; ++j)
-    for (int k = 0; k <= j; ++k) Lk[(size_t)k * DP + j] = L[(size_t)j * d + k];
   HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(e->Lk.p, Lk.data(), Lk.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (e->wide) {  // the shared factor's tiles: buffer 0 of the factor and of its diagonal tiles (a shared factor is never swapped)
+    std::vector<double> fac, ud;
+    wide_factor_pack_host(L, d, fac, ud);
+    HIP_TRY(hipMemcpy(e->Lk.p, fac.data(), fac.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->wide_ud.p, ud.data(), ud.size() * sizeof(double), hipMemcpyHostToDevice));
+  } else {
+    std::vector<double> Lk((size_t)DP * DP, 0.0);
+    for (int j = 0; j < d; ++j)
+      for (int k = 0; k <= j; ++k) Lk[(size_t)k * DP + j] = L[(size_t)j * d + k];
+    HIP_TRY(hipMemcpy(e->Lk.p, Lk.data(), Lk.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
   e->prop_C_h = Ch;
   e->L_identity = false;
   return TDA_OK;
@@ -209,8 +221,17 @@ int tda_engine_set_state(tda_engine* e, const void* blob, int64_t bytes) {
   }
   if (e->L_identity) {  // derived from the factor at init(): the restored one may come from tda_engine_set_proposal_covariance
     const int d = e->d, DP = e->DP;
-    std::vector<double> Lh((size_t)DP * DP);
-    HIP_TRY(hipMemcpy(Lh.data(), e->Lk.p, Lh.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> Lh((size_t)DP * DP, 0.0);
+    if (e->wide) {  // (65 .. 128 parameters: the shared factor's tiles, buffer 0; dense again, k-major like the narrow factor)
+      std::vector<double> f(WIDE_FACTOR_DOUBLES), u(WIDE_UD_DOUBLES), L;
+      HIP_TRY(hipMemcpy(f.data(), e->Lk.p, f.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(u.data(), e->wide_ud.p, u.size() * sizeof(double), hipMemcpyDeviceToHost));
+      wide_factor_unpack_host(f.data(), u.data(), d, L);
+      for (int j = 0; j < d; ++j)
+        for (int k = 0; k <= j; ++k) Lh[(size_t)k * DP + j] = L[(size_t)j * d + k];
+    } else {
+      HIP_TRY(hipMemcpy(Lh.data(), e->Lk.p, Lh.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
     for (int k = 0; k < d && e->L_identity; ++k)
       for (int j = 0; j < d; ++j)
         if (Lh[(size_t)k * DP + j] != (j == k ? 1.0 : 0.0)) {

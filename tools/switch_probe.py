@@ -1,6 +1,6 @@
 """One seeded run of a configuration whose kernel choice an environment switch changes; records to an .npz.  The switches are
 read once per process, so A/B comparisons start this script twice (tests/test_gpu_switches.py).
-    python tools/switch_probe.py {mlda3|mlda3_short|da2|aemd|aemd_lean|aem_dense|aem_dense_da_pcn|aem_dense_m200|aem_dense_chunks|dream|am|am_d24}[_ragged] out.npz     (_ragged: a chain count that is not a multiple of the 16-chain tile)"""
+    python tools/switch_probe.py {mlda3|mlda3_short|da2|da2_wide_am|da2_wide_grw|aemd|aemd_lean|aem_dense|aem_dense_da_pcn|aem_dense_m200|aem_dense_chunks|dream|am|am_d24}[_ragged] out.npz     (_ragged: a chain count that is not a multiple of the 16-chain tile)"""
 import os
 import sys
 
@@ -24,6 +24,9 @@ def hierarchy(ms, sl, kind, n_fine, N=256, d=64, error_model=None):
             e.set_level(k, A, A @ truth + 0.1 * rng.standard_normal(m), 0, 0.01)
     if kind == "am":
         e.set_proposal(2, 1e-4 * np.eye(d), t0=20, period=20)
+    elif kind == "grw":  # a shared factor that is not the identity: increments by k_apply / k_wide_apply, not k_rng_direct
+        B = rng.standard_normal((d, d))
+        e.set_proposal(0, 1e-4 * (np.eye(d) + 0.3 * B @ B.T / d), scaling=0.9)
     else:
         e.set_proposal(1, None, scaling=0.02)
     e.set_subchains(sl)
@@ -82,6 +85,10 @@ if __name__ == "__main__":
         res = hierarchy((128, 256, 512), [5, 3], "am", 5, N=64)
     elif what == "da2":
         res = hierarchy((256, 1024), [10], "pcn", 8, N=256 - cut)
+    elif what == "da2_wide_am":  # 96 parameters (tda_kernels_wide.h): the head-of-block k_wide_apply and the swap's chol + apply
+        res = hierarchy((40, 120), [5], "am", 12, N=48 - cut, d=96)
+    elif what == "da2_wide_grw":  # 96 parameters, a shared non-identity factor: the head-of-block k_wide_apply
+        res = hierarchy((40, 120), [5], "grw", 8, N=48 - cut, d=96)
     elif what == "aemd":
         res = hierarchy((200, 200, 200), [5, 3], "am", 8, N=96 - cut, error_model="state-independent-diagonal")
     elif what == "aemd_lean":  # at most 128 outputs: the base subchains are eligible for k_da_steps
