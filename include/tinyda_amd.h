@@ -99,7 +99,8 @@ typedef struct tda_config {
   int64_t n_chains;      /* chains held by this engine (rows of the state matrix) */
   int64_t chain_offset;  /* global id of local chain 0 */
   int32_t dim;           /* parameter dimension d: 1..64; 0.5: 65..128 for single-level chains and hierarchies of two to four levels (linear models, tda_engine_set_level_source and tda_engine_set_level_callback; error models: the dense one)
-                          * with linear models, source-defined models or host callbacks, isotropic / diagonal noise, any prior the engine knows and TDA_PROP_GRW / TDA_PROP_PCN / TDA_PROP_AM --
+                          * with linear models, source-defined models or host callbacks, isotropic / diagonal noise, any prior the engine knows and TDA_PROP_GRW / TDA_PROP_PCN / TDA_PROP_AM
+                          * (TDA_PROP_MALA: single-level source-defined models with tda_gradient, see tda_engine_set_level_source) --
                           * anything else at more than 64 parameters is refused by tda_engine_init with TDA_ERR_UNSUPPORTED */
   int32_t n_levels;      /* 1 = MH (sampler.py:213), 2 = Delayed Acceptance (:231), 3..6 = MLDA (:260); 0.5: 5 and 6 for the engine's own models without error model,
                           * dense observation covariance or DREAM(Z), dim <= 64 (0.4: at most 4) */
@@ -378,7 +379,14 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
  * (GRW / pCN / AM fused; DREAM(Z) step by step), and any level of a Delayed Acceptance / MLDA hierarchy: there the engine
  * sequences the levels from the host and a level step is propose -> tda_user_eval (compiled with the model) -> accept on
  * the stream; hierarchies may mix source-defined, callback and linear (iso / diag / adaptive noise) levels.
- * A source that does not compile returns TDA_ERR_INVALID with the compiler log in tda_last_error(). */
+ * A source that does not compile returns TDA_ERR_INVALID with the compiler log in tda_last_error().
+ * 0.5, MALA (TDA_PROP_MALA): the source may additionally define the model's vector-Jacobian product
+ *     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
+ *     // (J(theta)^T sensitivity)_j, 0 <= j < dim -- the reference's model.gradient(parameters, sensitivity)
+ * called with the sensitivity Sigma^-1 (y - F(theta)) of all n_outputs outputs; the engine adds the prior's gradient.  Single
+ * level, ISO / DIAG noise with m <= 2048, tda_engine_set_prior with a diagonal covariance, dim up to 128.  tda_engine_init
+ * compiles the MALA kernels as a second program; a source without tda_gradient returns TDA_ERR_INVALID naming it, JointPrior,
+ * dense or adaptive noise and more outputs TDA_ERR_UNSUPPORTED. */
 int tda_engine_set_level_source(tda_engine* e, int level, const char* source, int32_t m, const double* data,
                                 int32_t noise_kind, const double* noise);
 

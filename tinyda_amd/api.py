@@ -61,7 +61,8 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
             # and JointPrior, GaussianRandomWalk / CrankNicolson / AdaptiveMetropolis
             pc = np.asarray(low["prior_cov"])
             if ((len(posteriors) >= 2 and error_model is not None and diagonal_error_model) or len(posteriors) > MAX_LEVELS_FULL
-                    or type(proposal) not in (GaussianRandomWalk, CrankNicolson, AdaptiveMetropolis)
+                    or (type(proposal) not in (GaussianRandomWalk, CrankNicolson, AdaptiveMetropolis)
+                        and not (type(proposal) is MALA and len(posteriors) == 1 and low.get("has_gradient")))  # (MALA: a source-defined model's tda_gradient)
                     or (low.get("A") is None and "batched" not in low and "source" not in low)  # (linear, source-defined and batched host models)
                     or getattr(proposal, "block_moments", False)
                     or "rosenbrock" in low
@@ -130,8 +131,17 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
                         or (low["noise_kind"] == _lib.NOISE_ADAPTIVE and i < len(lows) - 1))
             if not ok_noise or np.count_nonzero(low["prior_cov"] - np.diag(np.diag(low["prior_cov"]))):
                 return _no("callback / source-defined models need isotropic / diagonal noise (dense: top level only) and a diagonal prior covariance")
-    if isinstance(proposal, MALA):  # exact gradient of a linear-Gaussian posterior: single level, linear model, Gaussian prior
-        if len(posteriors) != 1 or "source" in lows[0] or "batched" in lows[0] or "rosenbrock" in lows[0] or "prior_joint" in lows[0]:
+    if isinstance(proposal, MALA):
+        # exact gradient: of a linear-Gaussian posterior (single level, linear model, Gaussian prior), or from a source-defined
+        # model's own tda_gradient (single level, iso / diag noise, diagonal Gaussian prior: tda_user_mala_steps)
+        low = lows[0]
+        if len(posteriors) == 1 and "source" in low and "prior_joint" not in low:
+            if not low["has_gradient"]:
+                return _no("MALA over a source-defined model needs __device__ double tda_gradient(const double* theta, int dim, "
+                           "const double* sensitivity, int n_outputs, int j) in the model source")
+            if low["noise_kind"] not in (_lib.NOISE_ISO, _lib.NOISE_DIAG) or np.asarray(low["data"]).shape[0] > 2048:
+                return _no("MALA over a source-defined model: isotropic or diagonal noise, at most 2048 outputs")
+        elif len(posteriors) != 1 or "source" in lows[0] or "batched" in lows[0] or "rosenbrock" in lows[0] or "prior_joint" in lows[0]:
             return _no("MALA: single level, linear model, Gaussian prior")
     if isinstance(proposal, OperatorWeightedCrankNicolson):  # single level; fixed operators: linear, callback or source-defined model
         if len(posteriors) != 1 or proposal._lowering() is None or "rosenbrock" in lows[0] or "prior_joint" in lows[0]:

@@ -300,6 +300,9 @@ struct Level {
   }
   hipModule_t umod = nullptr;
   hipFunction_t ufn = nullptr, ufn_eval = nullptr, ufn_level = nullptr;
+  std::string usrc;                  // the model source (the MALA program is compiled from it at init)
+  hipModule_t umod_mala = nullptr;   // tda_user_mala_steps / tda_user_mala_grad0 (compile_user_mala)
+  hipFunction_t ufn_mala = nullptr, ufn_mala_grad0 = nullptr;
   DevBuf<double> udata, uw;
   double ros_a = 1.0, ros_b = 10.0, ros_data = 0.0;
   DevBuf<double> Apk, ytil, w, Ppk;
@@ -332,6 +335,7 @@ struct tda_engine {
   int prior_kind = tda::PRIOR_DIAG;
   bool prior_is_standard = false;  // N(0, I): the single-level tile kernel skips the constant loads
   bool prior_bounded = false;      // JointPrior with uniform components: support bounds in prior_lo / prior_hi
+  bool prior_joint = false;        // set by tda_engine_set_prior_joint (MALA over a source-defined model refuses it)
   double prior_logconst = 0.0;
   std::vector<double> prior_mean_h, prior_cov_h, prior_L_h;
   DevBuf<double> prior_lo, prior_hi;
@@ -983,6 +987,29 @@ int fill_user_args(tda_engine* e, const Level& lv, UserStepArgs& ua) {
   return TDA_OK;
 }
 
+// MALA over a source-defined model: everything but the block (S, inc, u, records)
+int fill_user_mala_args(tda_engine* e, const Level& lv, UserMalaArgs& ga) {
+  if (e->prior_kind == PRIOR_DENSE) return fail(TDA_ERR_UNSUPPORTED, "source-defined forward models need a diagonal prior covariance");
+  ga.N = e->N;
+  ga.NP = e->NP;
+  ga.d = e->d;
+  ga.DP = e->DP;
+  ga.m = lv.m;
+  ga.theta = e->theta.p;
+  ga.lp = e->lp.p;
+  ga.ll = e->ll.p;
+  ga.grad = e->mala_grad.p;
+  ga.scaling = e->scaling.p;
+  ga.acc_count = e->acc_count.p;
+  ga.data = lv.udata.p;
+  ga.w = lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr;
+  ga.var = lv.var;
+  ga.pr_mean = e->prior_mean.p;
+  ga.pr_pinv = e->prior_pinv.p;
+  ga.logconst = e->prior_logconst;
+  return TDA_OK;
+}
+
 constexpr int MODEL_CALLBACK = 3;
 
 void fill_ext_args(tda_engine* e, const Level& lv, ExtArgs& xa) {
@@ -1274,6 +1301,7 @@ void tda_engine_destroy(tda_engine* e) {
   }
   for (auto& lv : e->levels) {
     if (lv.umod) (void)hipModuleUnload(lv.umod);
+    if (lv.umod_mala) (void)hipModuleUnload(lv.umod_mala);
     lv.release_callback_buffers();
   }
   if (e->copy_stream) {

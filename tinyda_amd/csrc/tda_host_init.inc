@@ -14,8 +14,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "a dense observation covariance in a hierarchy: at most %d levels", (int)AEM_MAXLEV);
   }
   if (e->wide) {  // 65 .. 128 parameters (tda_kernels_wide.h): what that path is built for
-    if (e->is_dreamz || (e->pp.kind != TDA_PROP_GRW && e->pp.kind != TDA_PROP_PCN && e->pp.kind != TDA_PROP_AM))
-      return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: GaussianRandomWalk, CrankNicolson and AdaptiveMetropolis are lowered");
+    const bool user_mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA && e->nlev == 1 && e->levels[0].model == MODEL_USER;
+    if (e->is_dreamz || (e->pp.kind != TDA_PROP_GRW && e->pp.kind != TDA_PROP_PCN && e->pp.kind != TDA_PROP_AM && !user_mala))
+      return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: GaussianRandomWalk, CrankNicolson and AdaptiveMetropolis are lowered (MALA: single-level source-defined models)");
     if (e->pp.kind == TDA_PROP_AM && e->pp.block_moments) return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: block_moments is not lowered");
     for (const Level& l0 : e->levels) {
       // (a batched host callback, single level or in a host-sequenced hierarchy: k_ext_propose / k_ext_accept / k_ext_level_action take a
@@ -39,9 +40,17 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "operator-weighted pCN needs a Gaussian prior");
   }
   if (e->prop_set && !e->is_dreamz && e->pp.kind == TDA_PROP_MALA) {
-    if (e->levels[0].model != MODEL_LINEAR) return fail(TDA_ERR_UNSUPPORTED, "MALA is lowered for linear forward models only (exact gradient)");
+    const Level& l0 = e->levels[0];
+    if (l0.model != MODEL_LINEAR && l0.model != MODEL_USER)
+      return fail(TDA_ERR_UNSUPPORTED, "MALA is lowered for linear and source-defined forward models only (exact gradient)");
     if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "MALA needs a Gaussian prior");
-    if (e->levels[0].noise_kind == TDA_NOISE_ADAPTIVE) return fail(TDA_ERR_UNSUPPORTED, "MALA: adaptive likelihoods are not lowered");
+    if (l0.noise_kind == TDA_NOISE_ADAPTIVE) return fail(TDA_ERR_UNSUPPORTED, "MALA: adaptive likelihoods are not lowered");
+    if (l0.model == MODEL_USER) {  // tda_user_mala_steps: iso / diag noise, diagonal Gaussian prior, sensitivity of m <= 2048 outputs in LDS
+      if (e->prior_joint || e->prior_kind == PRIOR_DENSE)
+        return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model needs a multivariate normal prior with diagonal covariance");
+      if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: isotropic or diagonal noise");
+      if (l0.m > 2048) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: at most 2048 outputs");
+    }
   }
   {
     int n_cb = 0;
@@ -223,16 +232,29 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     if (e->nlev == 1) return TDA_OK;
   }
   const bool owcn = !e->is_dreamz && e->pp.kind == TDA_PROP_OWCN, mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA;
+  const bool user_mala = mala && e->levels[0].model == MODEL_USER;
+  if (user_mala && !e->levels[0].umod_mala) {  // the second program: GRW / pCN / AM engines never build it
+    Level& l0 = e->levels[0];
+    if ((rc = compile_user_mala(l0.usrc, &l0.umod_mala, &l0.ufn_mala, &l0.ufn_mala_grad0))) return rc;
+  }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;
   const double* Cuse = (e->pp.kind == TDA_PROP_PCN || owcn) ? e->prior_cov_h.data() : e->prop_C_h.data();  // proposal.py:336-341
   if (!mala && !cholesky_host(Cuse, d, L)) return fail(TDA_ERR_NUMERIC, "proposal covariance is not positive definite");
   std::vector<double> Lk((size_t)DP * DP, 0.0);
-  if (mala) {
-    // np.random.normal(size = d) (proposal.py:955): unit factor.  Gradient of the log-posterior of the linear-Gaussian
-    // target (proposal.py:986-998; utils.py:273-287) in closed form: grad = c - H theta with
-    //   H = Sigma_prior^-1 + A^T Sigma_e^-1 A,   c = Sigma_prior^-1 mu + A^T Sigma_e^-1 (data - b)
+  if (mala) {  // np.random.normal(size = d) (proposal.py:955): unit factor
     for (int j = 0; j < d; ++j) Lk[(size_t)j * DP + j] = 1.0;
+    L.assign((size_t)d * d, 0.0);  // (65 .. 128 parameters: packed into tiles below)
+    for (int j = 0; j < d; ++j) L[(size_t)j * d + j] = 1.0;
+  }
+  if (user_mala) {
+    // source-defined model: the gradient comes from the model's own tda_gradient at every step (tda_user_mala_steps)
+    if ((rc = e->mala_grad.alloc((size_t)NP * DP))) return rc;
+    HIP_TRY(hipMemsetAsync(e->mala_grad.p, 0, (size_t)NP * DP * sizeof(double), e->stream));
+  } else if (mala) {
+    // linear model: gradient of the log-posterior of the linear-Gaussian target (proposal.py:986-998; utils.py:273-287) in
+    // closed form, grad = c - H theta with
+    //   H = Sigma_prior^-1 + A^T Sigma_e^-1 A,   c = Sigma_prior^-1 mu + A^T Sigma_e^-1 (data - b)
     const Level& lv0 = e->levels[0];
     const int m = lv0.m;
     std::vector<double> Wp, H((size_t)DP * DP, 0.0), cv(DP, 0.0);
@@ -382,7 +404,11 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   e->exp_pos = 0;
   // initial links (chain.py:70)
   if ((rc = launch_eval(e, 0, e->theta.p, e->lp.p, e->ll.p))) return rc;
-  if (mala) {
+  if (user_mala) {
+    UserMalaArgs ga{};
+    if ((rc = fill_user_mala_args(e, e->levels[0], ga))) return rc;
+    if ((rc = launch_user_mala(e->levels[0].ufn_mala_grad0, ga, e->stream))) return rc;
+  } else if (mala) {
     const int64_t nt = NP * DP;
     hipLaunchKernelGGL(k_mala_grad0, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, e->stream, NP, DP, e->mala_H.p, e->mala_c.p,
                        e->theta.p, e->mala_grad.p);

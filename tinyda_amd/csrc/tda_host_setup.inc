@@ -51,6 +51,7 @@ int tda_engine_set_prior(tda_engine* e, const double* mean, const double* cov) {
   if ((rc = e->prior_pinv.upload(ph))) return rc;
   e->prior_logconst = d * std::log(2.0 * M_PI) + logdet;
   e->prior_bounded = false;
+  e->prior_joint = false;
   e->prior_set = true;
   return TDA_OK;
 }
@@ -94,6 +95,7 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
   e->prior_ncb = 0;
   e->prior_logconst = logconst;
   e->prior_bounded = bounded;
+  e->prior_joint = true;
   e->prior_set = true;
   return TDA_OK;
 }
@@ -308,8 +310,15 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
     lv.ufn_eval = nullptr;
     lv.ufn_level = nullptr;
   }
+  if (lv.umod_mala) {
+    (void)hipModuleUnload(lv.umod_mala);
+    lv.umod_mala = nullptr;
+    lv.ufn_mala = nullptr;
+    lv.ufn_mala_grad0 = nullptr;
+  }
   int rc = compile_user_model(source, &lv.umod, &lv.ufn, &lv.ufn_eval, &lv.ufn_level);
   if (rc) return rc;
+  lv.usrc = source;
   std::vector<double> y(data, data + m), w;
   if (noise_kind == TDA_NOISE_ADAPTIVE) {
     if ((rc = ext_level_adaptive(e, lv, m, data, noise))) return rc;

@@ -354,6 +354,18 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
         int xrc = ext_step(e, lv, xa);
         if (xrc) return xrc;
       }
+    } else if (lv.model == MODEL_USER && e->pp.kind == TDA_PROP_MALA) {
+      UserMalaArgs ga{};
+      int urc = fill_user_mala_args(e, lv, ga);
+      if (urc) return urc;
+      ga.S = (int)S;
+      ga.inc = sa.inc;
+      ga.u = sa.u;
+      ga.rec_params = sa.rec_params;
+      ga.rec_stats = sa.rec_stats;
+      ga.rec_acc = sa.rec_acc;
+      ScopedTimer tm(e, 1);
+      if ((urc = launch_user_mala(lv.ufn_mala, ga, e->stream))) return urc;
     } else if (lv.model == MODEL_USER) {
       UserStepArgs ua{};
       int urc = fill_user_args(e, lv, ua);

@@ -4,6 +4,10 @@
 // through the host protocol (the reference evaluates a Python callable per chain and step, posterior.py:95-96).
 // One wave per chain: lane j owns parameter j, the lanes stride over the outputs.  Same step semantics, records and
 // RNG inputs as k_mh_steps; proposals, adaptation and Cholesky stay the engine's own kernels.
+// MALA (0.5) additionally needs the model's vector-Jacobian product,
+//     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
+// = (J(theta)^T sensitivity)_j (the reference's model.gradient(parameters, sensitivity), proposal.py:996-998); its kernels are a
+// second program, compiled at init only when the proposal is MALA.
 #include <hip/hiprtc.h>
 
 namespace {
@@ -292,32 +296,242 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int 
 }
 )SRC";
 
-// compile prelude + user source + kernel for gfx950; on failure the hiprtc log goes into the error message
-int compile_user_model(const char* source, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_eval, hipFunction_t* fn_level) {
-  std::string src = std::string(kUserPrelude) + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kUserKernel;
+// MALA over a source-defined model (proposal.py:945-984): single level, iso / diag noise, diagonal Gaussian prior.  The
+// gradient of the log-posterior at the current state is chain state ([NP][DP], like theta; checkpoint blobs carry it).
+struct UserMalaArgs {
+  long long N, NP;
+  int d, DP, m, S;
+  double* theta;
+  double* lp;
+  double* ll;
+  double* grad;
+  const double* scaling;
+  int* acc_count;
+  const double* inc;  // unit normals [S][NP][DP] (the proposal factor is the identity)
+  const double* u;
+  const double* data;
+  const double* w;  // 1 / diag(noise) or null (isotropic)
+  double var;
+  const double* pr_mean;
+  const double* pr_pinv;
+  double logconst;
+  double* rec_params;
+  double* rec_stats;
+  unsigned char* rec_acc;
+};
+
+// (before the user source: the fallback a call resolves to when the source defines no tda_gradient of the contract's signature --
+// a non-template function of that signature wins overload resolution against it)
+const char* const kMalaPrelude = R"SRC(
+struct tda_gradient_missing {};
+template <class J>
+__device__ tda_gradient_missing tda_gradient(const double*, int, const double*, int, J) { return {}; }
+)SRC";
+
+const char* const kMalaKernel = R"SRC(
+static_assert(!__is_same(decltype(tda_gradient((const double*)nullptr, 0, (const double*)nullptr, 0, 0)), tda_gradient_missing),
+              "tda_gradient_missing: MALA needs __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)");
+struct UserMalaArgs {
+  long long N, NP;
+  int d, DP, m, S;
+  double* theta;
+  double* lp;
+  double* ll;
+  double* grad;
+  const double* scaling;
+  int* acc_count;
+  const double* inc;
+  const double* u;
+  const double* data;
+  const double* w;
+  double var;
+  const double* pr_mean;
+  const double* pr_pinv;
+  double logconst;
+  double* rec_params;
+  double* rec_stats;
+  unsigned char* rec_acc;
+};
+__device__ __forceinline__ double tda_wave_sum(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// outputs of the model at the parameters in s_th: returns this lane's share of the weighted sum of squares and leaves the
+// sensitivity grad_loglike = Sigma^-1 (y - F) in s_sens (distributions.py:300-301 iso: 1 / var * r, :314-315 diag: w * r)
+__device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, int lane) {
+  const double iv = 1.0 / a.var;
+  double sse = 0.0;
+  for (int o = lane; o < a.m; o += 64) {
+    const double f = tda_forward(s_th, a.d, o);
+    const double r = f - a.data[o];
+    double sq = r * r;
+    if (a.w) sq *= a.w[o];
+    sse += sq;
+    s_sens[o] = (a.w ? a.w[o] : iv) * (a.data[o] - f);
+  }
+  return sse;
+}
+// one wave per chain: lane j owns parameter j (and j + 64 at 65 .. 128 parameters), the lanes stride over the outputs
+extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
+  extern __shared__ double s_sens[];  // [m]
+  __shared__ double s_th[128];
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const size_t row = (size_t)c * a.DP;
+  double cur = lj ? a.theta[row + lane] : 0.0, cur2 = lj2 ? a.theta[row + lane2] : 0.0;
+  double gc = lj ? a.grad[row + lane] : 0.0, gc2 = lj2 ? a.grad[row + lane2] : 0.0;  // gradient at the current state
+  double lp = a.lp[c], ll = a.ll[c];
+  const double sg = a.scaling[c], h = 0.5 * sg * sg, kq = -0.5 / (sg * sg);  // proposal.py:953, :1002
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+  int nacc = 0;
+  for (int s = 0; s < a.S; ++s) {
+    const double* z = a.inc + ((size_t)s * a.NP + c) * a.DP;
+    const double prp = lj ? (cur + h * gc) + sg * z[lane] : 0.0;  // proposal.py:951-956
+    const double prp2 = lj2 ? (cur2 + h * gc2) + sg * z[lane2] : 0.0;
+    __syncthreads();  // (the previous step's readers of s_th / s_sens are done)
+    s_th[lane] = prp;
+    s_th[lane2] = prp2;
+    __syncthreads();
+    const double sse = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, lane));
+    double pj = 0.0;
+    if (lj) {
+      const double dv = prp - pm;
+      pj = dv * dv * pinv;
+    }
+    if (lj2) {
+      const double dv2 = prp2 - pm2;
+      pj += dv2 * dv2 * pinv2;
+    }
+    const double maha = tda_wave_sum(pj);
+    const double ll_n = a.w ? -0.5 * sse : -0.5 * sse / a.var;
+    const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
+    const double post_n = lp_n + ll_n;               // link.py:48
+    __syncthreads();  // s_sens complete
+    // gradient at the proposal: grad log prior + J^T grad loglike (proposal.py:996-998; utils.py:273-287)
+    const double gp = lj ? pinv * (pm - prp) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+    const double gp2 = lj2 ? pinv2 * (pm2 - prp2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+    // transition densities (proposal.py:1000-1005): q(x|y) = -|x - y - s^2/2 grad(y)|^2 / (2 s^2)
+    const double da = (cur - prp) - h * gp, da2 = (cur2 - prp2) - h * gp2;
+    const double db = (prp - cur) - h * gc, db2 = (prp2 - cur2) - h * gc2;
+    const double qa = tda_wave_sum(da * da + da2 * da2), qb = tda_wave_sum(db * db + db2 * db2);
+    double alpha = exp(((post_n - (lp + ll)) + kq * qa) - kq * qb);  // proposal.py:976-984
+    if (post_n != post_n) alpha = 0.0;
+    const bool acc = a.u[(size_t)s * a.NP + c] < alpha;  // chain.py:112
+    if (acc) {
+      lp = lp_n;
+      ll = ll_n;
+      cur = prp;
+      cur2 = prp2;
+      gc = gp;
+      gc2 = gp2;
+    }
+    nacc += acc ? 1 : 0;
+    const size_t r = (size_t)s * a.N + c;
+    if (lane == 0) {
+      if (a.rec_stats) {
+        a.rec_stats[r * 3 + 0] = lp;
+        a.rec_stats[r * 3 + 1] = ll;
+        a.rec_stats[r * 3 + 2] = lp + ll;
+      }
+      if (a.rec_acc) a.rec_acc[r] = acc ? 1 : 0;
+    }
+    if (a.rec_params && lj) a.rec_params[r * a.d + lane] = cur;
+    if (a.rec_params && lj2) a.rec_params[r * a.d + lane2] = cur2;
+  }
+  if (lane < a.DP) {
+    a.theta[row + lane] = cur;
+    a.grad[row + lane] = gc;
+  }
+  if (lane2 < a.DP) {
+    a.theta[row + lane2] = cur2;
+    a.grad[row + lane2] = gc2;
+  }
+  if (lane == 0) {
+    a.lp[c] = lp;
+    a.ll[c] = ll;
+    if (a.acc_count) a.acc_count[c] += nacc;
+  }
+}
+// gradient of the log-posterior at the current states (init; the padding of a row is written as zero)
+extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserMalaArgs a) {
+  extern __shared__ double s_sens[];
+  __shared__ double s_th[128];
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const size_t row = (size_t)c * a.DP;
+  const double th = lj ? a.theta[row + lane] : 0.0, th2 = lj2 ? a.theta[row + lane2] : 0.0;
+  s_th[lane] = th;
+  s_th[lane2] = th2;
+  __syncthreads();
+  (void)tda_mala_outputs(a, s_th, s_sens, lane);
+  __syncthreads();
+  if (lane < a.DP) a.grad[row + lane] = lj ? a.pr_pinv[lane] * (a.pr_mean[lane] - th) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? a.pr_pinv[lane2] * (a.pr_mean[lane2] - th2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+}
+)SRC";
+
+// hiprtc for gfx950; on failure `log` holds the (truncated) compiler log and `code` stays empty
+int hiprtc_gfx950(const std::string& src, const char* name, std::vector<char>& code, std::string& log) {
   hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, src.c_str(), "tda_user_model.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
+  if (hiprtcCreateProgram(&prog, src.c_str(), name, 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     return fail(TDA_ERR_HIP, "hiprtcCreateProgram failed");
   const char* opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
   if (cr != HIPRTC_SUCCESS) {
     size_t n = 0;
     (void)hiprtcGetProgramLogSize(prog, &n);
-    std::string log(n, '\0');
+    log.assign(n, '\0');
     if (n) (void)hiprtcGetProgramLog(prog, &log[0]);
     (void)hiprtcDestroyProgram(&prog);
-    if (log.size() > 400) log.resize(400);
-    return fail(TDA_ERR_INVALID, "the forward-model source does not compile: %s", log.c_str());
+    return TDA_OK;
   }
   size_t nb = 0;
   (void)hiprtcGetCodeSize(prog, &nb);
-  std::vector<char> code(nb);
+  code.resize(nb);
   (void)hiprtcGetCode(prog, code.data());
   (void)hiprtcDestroyProgram(&prog);
+  return TDA_OK;
+}
+
+// compile prelude + user source + kernel for gfx950; on failure the hiprtc log goes into the error message
+int compile_user_model(const char* source, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_eval, hipFunction_t* fn_level) {
+  std::string src = std::string(kUserPrelude) + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kUserKernel;
+  std::vector<char> code;
+  std::string log;
+  if (int rc = hiprtc_gfx950(src, "tda_user_model.hip", code, log)) return rc;
+  if (code.empty()) {
+    if (log.size() > 400) log.resize(400);
+    return fail(TDA_ERR_INVALID, "the forward-model source does not compile: %s", log.c_str());
+  }
   HIP_TRY(hipModuleLoadData(mod, code.data()));
   HIP_TRY(hipModuleGetFunction(fn, *mod, "tda_user_steps"));
   HIP_TRY(hipModuleGetFunction(fn_eval, *mod, "tda_user_eval"));
   HIP_TRY(hipModuleGetFunction(fn_level, *mod, "tda_user_level_action"));
+  return TDA_OK;
+}
+
+// the MALA program: prelude + user source + MALA kernels.  A source without tda_gradient resolves the kernels' call to the
+// tagged fallback template of the prelude, which a static_assert turns into the message below (not an unresolved symbol at load).
+int compile_user_mala(const std::string& source, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_grad0) {
+  std::string src = std::string(kUserPrelude) + kMalaPrelude + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kMalaKernel;
+  std::vector<char> code;
+  std::string log;
+  if (int rc = hiprtc_gfx950(src, "tda_user_mala.hip", code, log)) return rc;
+  if (code.empty()) {
+    if (log.find("tda_gradient_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "MALA on a source-defined model: the source defines no __device__ double tda_gradient(const double* theta, "
+                                   "int dim, const double* sensitivity, int n_outputs, int j)");
+    if (log.size() > 400) log.resize(400);
+    return fail(TDA_ERR_INVALID, "the forward-model source does not compile with the MALA kernels: %s", log.c_str());
+  }
+  HIP_TRY(hipModuleLoadData(mod, code.data()));
+  HIP_TRY(hipModuleGetFunction(fn, *mod, "tda_user_mala_steps"));
+  HIP_TRY(hipModuleGetFunction(fn_grad0, *mod, "tda_user_mala_grad0"));
   return TDA_OK;
 }
 
@@ -332,6 +546,14 @@ int launch_user_level(hipFunction_t fn, UserLevelArgs& a, hipStream_t st) {
   size_t sz = sizeof(UserLevelArgs);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)a.N, 1, 1, 64, 1, 1, 0, st, nullptr, cfg));
+  return TDA_OK;
+}
+
+// one wave per chain, the sensitivity Sigma^-1 (y - F) of its m outputs in dynamic LDS
+int launch_user_mala(hipFunction_t fn, UserMalaArgs& a, hipStream_t st) {
+  size_t sz = sizeof(UserMalaArgs);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)a.N, 1, 1, 64, 1, 1, (unsigned)(a.m * sizeof(double)), st, nullptr, cfg));
   return TDA_OK;
 }
 

@@ -3,6 +3,8 @@
 tinyDA's model protocol is "callable theta -> ndarray or (ndarray, qoi)" (posterior.py:95-101).
 These classes honour it on the host and additionally expose what the HIP kernels need.
 """
+import re
+
 import numpy as np
 
 
@@ -45,20 +47,43 @@ class DeviceModel:
 
         __device__ double tda_forward(const double* theta, int dim, int o);   // output o of F(theta), 0 <= o < n_outputs
 
-    `reference`, if given, is a Python callable theta -> outputs used when the model is called on the host (host
-    protocol, tests); without it the model only runs on the device."""
+    and may define the model's vector-Jacobian product, which MALA runs on (the device counterpart of the reference's
+    `model.gradient(parameters, sensitivity)`, proposal.py:996-998):
 
-    def __init__(self, source, n_outputs, reference=None):
+        __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
+        // (J(theta)^T sensitivity)_j, 0 <= j < dim
+
+    `has_gradient` says whether the source defines it (comments do not count).
+
+    `reference`, if given, is a Python callable theta -> outputs used when the model is called on the host (host
+    protocol, tests); without it the model only runs on the device.  `reference_gradient(theta, sensitivity)`, if
+    given, becomes the model's `gradient` method, so the host MALA takes the exact-gradient branch (finite differences
+    otherwise)."""
+
+    def __init__(self, source, n_outputs, reference=None, reference_gradient=None):
         self.source = str(source)
         self.n_outputs = int(n_outputs)
         self.reference = reference
         if "tda_forward" not in self.source:
             raise ValueError("the source must define __device__ double tda_forward(const double* theta, int dim, int o)")
+        self.has_gradient = "tda_gradient" in _strip_comments(self.source)
+        self.reference_gradient = reference_gradient
+        if reference_gradient is not None:
+            self.gradient = self._reference_gradient  # (an attribute only then: MALA.setup_proposal looks for it)
+
+    def _reference_gradient(self, parameters, sensitivity):
+        return np.asarray(self.reference_gradient(np.asarray(parameters, dtype=np.float64), np.asarray(sensitivity, dtype=np.float64)),
+                          dtype=np.float64)
 
     def __call__(self, parameters):
         if self.reference is None:
             raise TypeError("this DeviceModel has no host reference implementation; run it with backend='hip'")
         return np.atleast_1d(np.asarray(self.reference(np.asarray(parameters, dtype=np.float64)), dtype=np.float64))
+
+
+def _strip_comments(source):
+    """HIP source without its // and /* */ comments (string literals are left alone)."""
+    return re.sub(r'//[^\n]*|/\*.*?\*/|("(?:\\.|[^"\\])*")', lambda mt: mt.group(1) or " ", source, flags=re.S)
 
 
 class BatchedModel:

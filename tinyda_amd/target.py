@@ -78,8 +78,8 @@ class Posterior:
             data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
             if data.shape != (self.model.n_outputs,):
                 return None
-            return dict(prior_mean=mean, prior_cov=cov, source=self.model.source, A=None, b=None, data=data,
-                        noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
+            return dict(prior_mean=mean, prior_cov=cov, source=self.model.source, has_gradient=self.model.has_gradient, A=None, b=None,
+                        data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
         if isinstance(self.model, BatchedModel):
             kind, noise = self.likelihood._lowering()
             data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
