@@ -9,69 +9,14 @@ import scipy.stats as st
 
 from oracle import tinyda_oracle as orc
 
+from .extmodel import GradLevel, np_forward, source  # the model, its NumPy twin and MALA gradient (tests/extmodel.py)
 from .test_mala_source import FORWARD_ONLY_SRC, ROSEN_SRC
 
 pytestmark = pytest.mark.gpu
 
-# F_o(theta) = sin(sum_j w_oj theta_j) + 0.5 theta_{o % d} theta_{(o + 1) % d}, w_oj = 0.1 + 0.01 ((7 o + 3 j) % 11); above
-# theta_0 > nan_above (if set) every output is NaN
-SRC_TEMPLATE = r"""
-__device__ __forceinline__ double w_oj(int o, int j) { return 0.1 + 0.01 * ((o * 7 + j * 3) % 11); }
-__device__ double tda_forward(const double* theta, int dim, int o) {
-  if (theta[0] > NAN_ABOVE) return __builtin_nan("");
-  double s = 0.0;
-  for (int j = 0; j < dim; ++j) s += w_oj(o, j) * theta[j];
-  return sin(s) + 0.5 * (theta[o % dim] * theta[(o + 1) % dim]);
-}
-__device__ double tda_gradient(const double* theta, int dim, const double* sens, int m, int j) {
-  double g = 0.0;
-  for (int o = 0; o < m; ++o) {
-    double s = 0.0;
-    for (int k = 0; k < dim; ++k) s += w_oj(o, k) * theta[k];
-    double dF = cos(s) * w_oj(o, j);
-    if (o % dim == j) dF += 0.5 * theta[(o + 1) % dim];
-    if ((o + 1) % dim == j) dF += 0.5 * theta[o % dim];
-    g += sens[o] * dF;
-  }
-  return g;
-}
-"""
-
 
 def _src(nan_above=None):
-    return SRC_TEMPLATE.replace("NAN_ABOVE", "1e300" if nan_above is None else repr(float(nan_above)))
-
-
-def _w(m, d):
-    return 0.1 + 0.01 * ((np.arange(m)[:, None] * 7 + np.arange(d)[None, :] * 3) % 11)
-
-
-def np_forward(theta, m, nan_above=None):
-    theta = np.atleast_2d(theta)
-    d = theta.shape[1]
-    o = np.arange(m)
-    F = np.sin(theta @ _w(m, d).T) + 0.5 * (theta[:, o % d] * theta[:, (o + 1) % d])
-    if nan_above is not None:
-        F[theta[:, 0] > nan_above] = np.nan
-    return F
-
-
-def np_vjp(theta, sens):
-    d, m = theta.shape[1], sens.shape[1]
-    W = _w(m, d)
-    g = (sens * np.cos(theta @ W.T)) @ W
-    for o in range(m):
-        g[:, o % d] += 0.5 * sens[:, o] * theta[:, (o + 1) % d]
-        g[:, (o + 1) % d] += 0.5 * sens[:, o] * theta[:, o % d]
-    return g
-
-
-class GradLevel(orc.CallableGaussianLevel):
-    """CallableGaussianLevel with MALA's gradient (proposal.py:996-998): grad log prior + J^T grad loglike."""
-
-    def grad_logpost(self, theta, F):
-        g_prior = (self.prior.mean[None, :] - theta) @ np.linalg.inv(self.prior.cov).T
-        return g_prior + np_vjp(theta, self.loglike.grad(F))
+    return source(nan_above)
 
 
 def test_engine_replays_reference_chain(golden):
