@@ -10,6 +10,12 @@ of every chain on the GPU (k_apply -> k_mh_steps (100 fused iterations: propose,
 log alpha, accept, record) -> k_adapt (the 100 moment updates) -> k_chol (covariance swap)), i.e. 409 600 proposal
 evaluations per GPU.  The driver's `--steps 20 --warmup 5` is SURVEY's C2 run: 2000 iterations per chain after a warm-up.
 
+A plain run does only what the headline needs: set-up (pilot run and burn-in), the warm-up steps, the timed steps,
+--dump-outputs, and the line (with `roofline`, `kernel_ms` and `acceptance_rate`, read off the timed steps themselves).
+`--full` adds the side measurements, each a run of its own after the headline: ESS/s (the timed window's and a stationary
+window), the `configs` block (the other BASELINE configurations) and the CPU baseline; `--no-ess`, `--no-configs` and
+`--no-cpu-baseline` leave one of them out.
+
 With --gpus N > 1 and no WORLD_SIZE in the environment this script starts its own N ranks
 (`python -m torch.distributed.run ...` as a child process, before anything here touches the GPU) and relays rank 0's line;
 under torch.distributed.run it is a rank.  Chains are sharded by global id, there is no data-path collective.
@@ -51,17 +57,20 @@ def parse_args():
     ap.add_argument("--burnin", type=int, default=80000,
                     help="set-up: untimed, unrecorded AdaptiveMetropolis iterations before the warm-up steps (the per-chain covariance "
                          "estimates need them: a 20 000-iteration window has R-hat 1.23 right after the pilot, 1.02 after 80 000)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also take the side measurements: ESS/s, the `configs` block and the CPU baseline "
+                         "(~30 s more; off by default)")
     ap.add_argument("--ess-iterations", type=int, default=20000,
-                    help="length of the separate stationary window ESS/s is measured on (0 = only the timed window)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: length of the separate stationary window ESS/s is measured on (0 = only the timed window)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-child", action="store_true", help="internal: run only the CPU legs and print their JSON")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="allow --gpus N with fewer than N devices: every rank on cuda:0 over gloo (same as TINYDA_BENCH_ONE_GPU=1)")
-    ap.add_argument("--no-ess", action="store_true")
+    ap.add_argument("--no-ess", action="store_true", help="--full without ESS/s")
     ap.add_argument("--extras", action="store_true", help="side measurements (other proposals / extensions), never the headline")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the `configs` block (the other BASELINE configurations at full chain counts, each with its own "
-                         "roofline: tools/bench_configs.py; rank 0 at N = 1 only, after the headline is measured, ~10 s)")
+                    help="--full without the `configs` block (the other BASELINE configurations at full chain counts, each with its "
+                         "own roofline: tools/bench_configs.py; rank 0 at N = 1 only, after the headline is measured, ~15 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0's chains, a fixed "
                          "sample of %d of them, float64 / float32, under 64 MB) so that two builds can be compared output for output"
@@ -421,7 +430,7 @@ def main():
             out["acceptance_rate"] = float(acc[:T_timed].float().mean().item())
         except Exception as exc:  # the headline must survive a failed side computation
             out["roofline_error"] = repr(exc)
-        if not args.no_ess:
+        if args.full and not args.no_ess:
             try:
                 out.update(ess_section(args, eng, diagnostics, params, stats, acc, rows, N, T_timed, dt, world, local_rank, burnin))
             except Exception as exc:
@@ -432,7 +441,7 @@ def main():
             out["extras"] = extras(Engine, diagnostics, A, y, N, K, W, params, stats, acc, rows, local_rank, rank)
         except Exception as exc:
             out["extras_error"] = repr(exc)
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         # the other BASELINE configurations (C2b, C3, C4 at exchange intervals 16 / 128, C5-literal, C5 + dense error model),
         # full per-GPU chain counts, each with its own roofline entry; side runs after the headline, never `value`
         try:
@@ -449,7 +458,7 @@ def main():
         except Exception as exc:
             out["configs_error"] = repr(exc)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the GPU result is complete: keep it on stderr in case anything below goes wrong (stdout carries ONE line, at the end)
             sys.stderr.write("[bench] GPU part done: %.4g %s, ms_per_step %.4f; CPU baseline legs follow (capped at %.0f s)\n"
                              % (out["value"], out["unit"], out["ms_per_step"], CPU_BASELINE_CAP_S))

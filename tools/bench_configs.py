@@ -1,6 +1,6 @@
 """The BASELINE configurations other than the headline (C2a is bench.py itself), each at its full per-GPU chain count, each with
-its own roofline entry.  bench.py imports `config_block()` and puts the list into its one JSON line as `"configs"`; run as a
-script it prints one JSON line per configuration.
+its own roofline entry.  bench.py --full imports `config_block()` and puts the list into its one JSON line as `"configs"`; run as
+a script it prints one JSON line per configuration.
 
     python tools/bench_configs.py                 every configuration
     python tools/bench_configs.py c3|c4 [K]|c5|c5aem M [n_fine]|c5aemd M|c2b|mala|c4peer|c4peerlag
