@@ -69,7 +69,8 @@ typedef enum tda_noise_kind {
   TDA_NOISE_ISO = 0,
   TDA_NOISE_DIAG = 1,
   TDA_NOISE_DENSE = 2,
-  TDA_NOISE_ADAPTIVE = 3 /* AdaptiveGaussianLogLike (distributions.py:332-449): dense covariance + per-chain bias */
+  TDA_NOISE_ADAPTIVE = 3, /* AdaptiveGaussianLogLike (distributions.py:332-449): dense covariance + per-chain bias */
+  TDA_NOISE_SOURCE = 4    /* extension: a separable log-likelihood defined by the level's HIP source (tda_engine_set_level_source only) */
 } tda_noise_kind;
 
 /* adaptive_error_model of sample() (sampler.py:82-87) */
@@ -386,7 +387,19 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
  * called with the sensitivity Sigma^-1 (y - F(theta)) of all n_outputs outputs; the engine adds the prior's gradient.  Single
  * level, ISO / DIAG noise with m <= 2048, tda_engine_set_prior with a diagonal covariance, dim up to 128.  tda_engine_init
  * compiles the MALA kernels as a second program; a source without tda_gradient returns TDA_ERR_INVALID naming it, JointPrior,
- * dense or adaptive noise and more outputs TDA_ERR_UNSUPPORTED. */
+ * dense or adaptive noise and more outputs TDA_ERR_UNSUPPORTED.
+ * Source-defined likelihood (TDA_NOISE_SOURCE; the reference takes any object with loglike(model_output), posterior.py:95-108):
+ * the source defines, after tda_forward, the terms of a separable log-likelihood log L(F) = sum_o term(F_o, y_o, p_o, o),
+ *     __device__ double tda_loglike_term(double f, double y, double p, int o);
+ *     __device__ double tda_loglike_term_grad(double f, double y, double p, int o);   // d term / d f (MALA only)
+ * with y = data (HOST [m]) and p = noise (HOST [m], one user parameter per output, passed on as given).  The functions are
+ * pure; the lane that computed output o calls them and the engine sums the terms.  A NaN or -inf term rejects the proposal.
+ * Lowered in the fused kernels only: single-level GRW / pCN / AM (dim up to 128, also tda_engine_set_prior_joint), any level of
+ * a hierarchy of up to four levels with fixed subchain lengths beside levels of any other kind, and single-level MALA with
+ * tda_gradient (the sensitivity is then d term / d f).  A source without tda_loglike_term (MALA: without
+ * tda_loglike_term_grad, at tda_engine_init) returns TDA_ERR_INVALID naming the signature.  tda_engine_init refuses it with
+ * TDA_ERR_UNSUPPORTED under DREAM(Z), Independence, operator-weighted pCN, an error model and randomised subchain lengths;
+ * tda_engine_set_level / _callback refuse the kind.  Likelihoods that couple outputs are not covered. */
 int tda_engine_set_level_source(tda_engine* e, int level, const char* source, int32_t m, const double* data,
                                 int32_t noise_kind, const double* noise);
 

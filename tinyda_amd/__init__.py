@@ -12,6 +12,7 @@ from .likelihoods import (  # noqa: F401
     JointPrior,
     AdaptiveGaussianLogLike,
     DefaultGaussianLogLike,
+    DeviceLogLike,
     DiagonalGaussianLogLike,
     GaussianLogLike,
     IsotropicGaussianLogLike,

@@ -43,9 +43,37 @@ def _no(reason):
     return None
 
 
-def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=None):
+def _loglike_source_refusal(low, n_levels, proposal, error_model, randomize):
+    """Why a level with a DeviceLogLike does not lower (None when it does): the likelihood exists inside the program compiled
+    with a DeviceModel only, so every route that evaluates a level's likelihood in the engine's own kernels is closed to it."""
+    if "loglike_source" not in low:
+        return "DeviceLogLike is compiled into the program of its level's model, which must be a DeviceModel"
+    if n_levels > MAX_LEVELS_FULL:
+        return "DeviceLogLike: hierarchies of at most %d levels" % MAX_LEVELS_FULL
+    if isinstance(proposal, DREAMZ):
+        return "DeviceLogLike is not lowered under DREAM(Z)"
+    if isinstance(proposal, OperatorWeightedCrankNicolson):
+        return "DeviceLogLike is not lowered under OperatorWeightedCrankNicolson"
+    if isinstance(proposal, IndependenceSampler):
+        return "DeviceLogLike is not lowered under IndependenceSampler"
+    if error_model is not None:
+        return "DeviceLogLike is not lowered together with an adaptive error model"
+    if randomize:
+        return "DeviceLogLike is not lowered with randomize_subchain_length"
+    if isinstance(proposal, MALA):
+        pc = np.asarray(low["prior_cov"])
+        if n_levels != 1 or "prior_joint" in low or np.count_nonzero(pc - np.diag(np.diag(pc))):
+            return "MALA with a DeviceLogLike: single level, multivariate normal prior with diagonal covariance"
+        if not low["loglike_has_gradient"]:
+            return ("MALA with a DeviceLogLike needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o) "
+                    "in the likelihood source")
+    return None
+
+
+def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=None, randomize=False):
     """Lowering pass: returns (list of level descriptions, proposal description) or None (the reason is left in _refusal).
-    error_model: sample()'s adaptive_error_model after its own validation (None / 'state-independent' / 'state-dependent')."""
+    error_model: sample()'s adaptive_error_model after its own validation (None / 'state-independent' / 'state-dependent');
+    randomize: its randomize_subchain_length."""
     del _refusal[:]
     if not 1 <= len(posteriors) <= MAX_LEVELS or type(proposal) not in _DEVICE_PROPOSALS:
         return _no("more than %d levels (or none), or a proposal class the engine has no kernel for (%s)" % (MAX_LEVELS, type(proposal).__name__))
@@ -56,6 +84,10 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
         low = getattr(post, "_lowering", lambda: None)()
         if low is None or low["prior_mean"].shape[0] > MAX_PARAMETERS:
             return _no("a posterior the engine cannot lower (an opaque Python model, a prior other than scipy's multivariate normal / JointPrior of norm and uniform, a likelihood outside GaussianLogLike's classes)" if low is None else "more than %d parameters" % MAX_PARAMETERS)
+        if low["noise_kind"] == _lib.NOISE_SOURCE:
+            why = _loglike_source_refusal(low, len(posteriors), proposal, error_model, randomize)
+            if why is not None:
+                return _no(why)
         if low["prior_mean"].shape[0] > 64:
             # 65 .. 128 parameters (0.5, tda_kernels_wide.h): single-level chains, Delayed Acceptance and MLDA (up to four levels), linear models with isotropic / diagonal noise, Gaussian priors (diagonal or dense covariance)
             # and JointPrior, GaussianRandomWalk / CrankNicolson / AdaptiveMetropolis
@@ -69,7 +101,7 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
                     or (("batched" in low or "source" in low) and np.count_nonzero(pc - np.diag(np.diag(pc))))  # (external models: diagonal prior covariance, as at any width)
                     or low["noise_kind"] not in ((_lib.NOISE_ISO, _lib.NOISE_DIAG, _lib.NOISE_ADAPTIVE) if (error_model is not None and not diagonal_error_model)
                                                  else (_lib.NOISE_ISO, _lib.NOISE_DIAG, _lib.NOISE_DENSE) if (len(posteriors) == 1 and low.get("A") is not None)
-                                                 else (_lib.NOISE_ISO, _lib.NOISE_DIAG))):
+                                                 else (_lib.NOISE_ISO, _lib.NOISE_DIAG, _lib.NOISE_SOURCE))):  # (NOISE_SOURCE: checked above)
                 return _no("more than 64 parameters are lowered for single-level chains, Delayed Acceptance and MLDA of linear, source-defined and batched host models with "
                            "isotropic / diagonal noise, GaussianRandomWalk / CrankNicolson / AdaptiveMetropolis (error models: the dense one)")
         if diagonal_error_model and low["noise_kind"] == _lib.NOISE_ADAPTIVE:
@@ -127,7 +159,7 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
             if any("rosenbrock" in low for low in lows) or type(proposal) not in (GaussianRandomWalk, CrankNicolson, AdaptiveMetropolis, DREAMZ):
                 return _no("hierarchies of callback / source-defined models run under GaussianRandomWalk / CrankNicolson / AdaptiveMetropolis / DREAMZ")
         for i, low in enumerate(lows):
-            ok_noise = (low["noise_kind"] in (_lib.NOISE_ISO, _lib.NOISE_DIAG) or (low["noise_kind"] == _lib.NOISE_DENSE and low["A"] is None)
+            ok_noise = (low["noise_kind"] in (_lib.NOISE_ISO, _lib.NOISE_DIAG, _lib.NOISE_SOURCE) or (low["noise_kind"] == _lib.NOISE_DENSE and low["A"] is None)
                         or (low["noise_kind"] == _lib.NOISE_ADAPTIVE and i < len(lows) - 1))
             if not ok_noise or np.count_nonzero(low["prior_cov"] - np.diag(np.diag(low["prior_cov"]))):
                 return _no("callback / source-defined models need isotropic / diagonal noise (dense: top level only) and a diagonal prior covariance")
@@ -139,7 +171,7 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
             if not low["has_gradient"]:
                 return _no("MALA over a source-defined model needs __device__ double tda_gradient(const double* theta, int dim, "
                            "const double* sensitivity, int n_outputs, int j) in the model source")
-            if low["noise_kind"] not in (_lib.NOISE_ISO, _lib.NOISE_DIAG) or np.asarray(low["data"]).shape[0] > 2048:
+            if low["noise_kind"] not in (_lib.NOISE_ISO, _lib.NOISE_DIAG, _lib.NOISE_SOURCE) or np.asarray(low["data"]).shape[0] > 2048:
                 return _no("MALA over a source-defined model: isotropic or diagonal noise, at most 2048 outputs")
         elif len(posteriors) != 1 or "source" in lows[0] or "batched" in lows[0] or "rosenbrock" in lows[0] or "prior_joint" in lows[0]:
             return _no("MALA: single level, linear model, Gaussian prior")
@@ -366,7 +398,8 @@ def sample(posteriors, proposal, iterations, n_chains=1, initial_parameters=None
     diag_aem = error_model_covariance == "diagonal" and n_levels > 1 and adaptive_error_model is not None
     if diag_aem and adaptive_error_model != "state-independent":
         raise ValueError("the diagonal error model is state-independent")
-    plan = None if backend == "host" else _device_plan(posteriors, proposal, diag_aem, adaptive_error_model if n_levels > 1 else None)
+    plan = None if backend == "host" else _device_plan(posteriors, proposal, diag_aem, adaptive_error_model if n_levels > 1 else None,
+                                                              bool(randomize_subchain_length) and n_levels > 1)
     why = list(_refusal)
     if plan is not None and isinstance(proposal, DREAMZ) and n_levels > 1 and diag_aem:
         plan = None  # (DREAMZ below a hierarchy runs with the reference's dense error model; the diagonal extension: host protocol)
@@ -378,7 +411,7 @@ def sample(posteriors, proposal, iterations, n_chains=1, initial_parameters=None
         # proposals, level logic, error model, adaptation and records on the device
         wrapped = _wrap_opaque_models(posteriors)
         if wrapped is not None:
-            plan = _device_plan(wrapped, proposal, diag_aem, adaptive_error_model)
+            plan = _device_plan(wrapped, proposal, diag_aem, adaptive_error_model, bool(randomize_subchain_length))
             if plan is not None:
                 posteriors = wrapped
             else:

@@ -304,6 +304,7 @@ struct Level {
   hipModule_t umod_mala = nullptr;   // tda_user_mala_steps / tda_user_mala_grad0 (compile_user_mala)
   hipFunction_t ufn_mala = nullptr, ufn_mala_grad0 = nullptr;
   DevBuf<double> udata, uw;
+  DevBuf<double> upar;  // TDA_NOISE_SOURCE: the per-output parameters of the source's tda_loglike_term (as given, not inverted)
   double ros_a = 1.0, ros_b = 10.0, ros_data = 0.0;
   DevBuf<double> Apk, ytil, w, Ppk;
   // adaptive error model: plain row-major copies for the wave-per-chain kernel
@@ -977,7 +978,7 @@ int fill_user_args(tda_engine* e, const Level& lv, UserStepArgs& ua) {
   ua.DP = e->DP;
   ua.m = lv.m;
   ua.data = lv.udata.p;
-  ua.w = lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr;
+  ua.w = lv.noise_kind == TDA_NOISE_SOURCE ? lv.upar.p : (lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr);
   ua.var = lv.var;
   ua.pr_mean = e->prior_mean.p;
   ua.pr_pinv = e->prior_pinv.p;
@@ -1002,7 +1003,7 @@ int fill_user_mala_args(tda_engine* e, const Level& lv, UserMalaArgs& ga) {
   ga.scaling = e->scaling.p;
   ga.acc_count = e->acc_count.p;
   ga.data = lv.udata.p;
-  ga.w = lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr;
+  ga.w = lv.noise_kind == TDA_NOISE_SOURCE ? lv.upar.p : (lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr);
   ga.var = lv.var;
   ga.pr_mean = e->prior_mean.p;
   ga.pr_pinv = e->prior_pinv.p;

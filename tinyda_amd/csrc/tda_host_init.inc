@@ -23,6 +23,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       // second parameter per lane)
       const bool model_ok = l0.model == MODEL_LINEAR || l0.model == MODEL_CALLBACK || l0.model == MODEL_USER;
       const bool noise_ok = l0.noise_kind == TDA_NOISE_ISO || l0.noise_kind == TDA_NOISE_DIAG || l0.noise_kind == TDA_NOISE_ADAPTIVE ||
+                            l0.noise_kind == TDA_NOISE_SOURCE ||  // (tda_user_steps / tda_user_level_action, refusals below)
                             (l0.noise_kind == TDA_NOISE_DENSE && e->nlev == 1 && l0.model == MODEL_LINEAR);  // (dense: the step kernel's own path, single level)
       if (!model_ok || !noise_ok)
         return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: linear, source-defined and host-callback forward models with isotropic or diagonal noise (single-level linear models: dense too) are lowered");
@@ -51,6 +52,17 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: isotropic or diagonal noise");
       if (l0.m > 2048) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: at most 2048 outputs");
     }
+  }
+  for (const Level& ls : e->levels) {
+    // a source-defined likelihood exists inside the level's hiprtc programs only (tda_user_steps, tda_user_level_action, the MALA
+    // kernels): every route that evaluates a source level's likelihood in the engine's own kernels would treat it as Gaussian
+    if (ls.noise_kind != TDA_NOISE_SOURCE) continue;
+    if (e->is_dreamz) return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood under DREAM(Z) is not lowered");
+    if (e->aem) return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood together with an error model is not lowered");
+    if (e->nlev > 1 && e->randomize) return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood with randomised subchain lengths is not lowered");
+    if (e->pp.kind == TDA_PROP_INDEPENDENCE || e->pp.kind == TDA_PROP_OWCN)
+      return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood under the Independence and operator-weighted pCN proposals is not lowered");
+    if (e->nlev > AEM_MAXLEV) return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood: hierarchies of at most %d levels", (int)AEM_MAXLEV);
   }
   {
     int n_cb = 0;
@@ -235,7 +247,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;
   if (user_mala && !e->levels[0].umod_mala) {  // the second program: GRW / pCN / AM engines never build it
     Level& l0 = e->levels[0];
-    if ((rc = compile_user_mala(l0.usrc, &l0.umod_mala, &l0.ufn_mala, &l0.ufn_mala_grad0))) return rc;
+    if ((rc = compile_user_mala(l0.usrc, l0.noise_kind == TDA_NOISE_SOURCE, &l0.umod_mala, &l0.ufn_mala, &l0.ufn_mala_grad0))) return rc;
   }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;

@@ -286,7 +286,7 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
         ua.nlev = nl;
         ua.q = q;
         ua.data = lq.udata.p;
-        ua.w = lq.noise_kind == TDA_NOISE_DIAG ? lq.uw.p : nullptr;
+        ua.w = lq.noise_kind == TDA_NOISE_SOURCE ? lq.upar.p : (lq.noise_kind == TDA_NOISE_DIAG ? lq.uw.p : nullptr);
         ua.var = lq.var;
         ua.theta = e->ml_theta.p;
         ua.lp = e->ml_lp.p;

@@ -107,6 +107,8 @@ int tda_engine_set_level(tda_engine* e, int level, int m, const double* A, const
   if (m < 1) return fail(TDA_ERR_INVALID, "m must be >= 1");
   HIP_TRY(hipSetDevice(e->cfg.device));
   Level& lv = e->levels[level];
+  if (noise_kind == TDA_NOISE_SOURCE)
+    return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood (TDA_NOISE_SOURCE) needs a source-defined forward model (tda_engine_set_level_source)");
   if (noise_kind < TDA_NOISE_ISO || noise_kind > TDA_NOISE_ADAPTIVE) return fail(TDA_ERR_INVALID, "noise_kind %d", noise_kind);
   if (noise_kind == TDA_NOISE_ADAPTIVE && m > AEM_MP_MAX)
     return fail(TDA_ERR_UNSUPPORTED, "AdaptiveGaussianLogLike on the device is limited to m <= %d observations (per-chain m x m state)", (int)AEM_MP_MAX);
@@ -299,7 +301,8 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
   if (!e || !source || !data || !noise) return fail(TDA_ERR_INVALID, "null argument");
   if (level < 0 || level >= (int)e->levels.size()) return fail(TDA_ERR_INVALID, "level %d out of range", level);
   if (m < 1) return fail(TDA_ERR_INVALID, "m must be >= 1");
-  if (noise_kind != TDA_NOISE_ISO && noise_kind != TDA_NOISE_DIAG && noise_kind != TDA_NOISE_DENSE && !(noise_kind == TDA_NOISE_ADAPTIVE && e->nlev > 1))
+  const bool loglike = noise_kind == TDA_NOISE_SOURCE;  // the likelihood is part of the source (tda_loglike_term), `noise` its parameters
+  if (!loglike && noise_kind != TDA_NOISE_ISO && noise_kind != TDA_NOISE_DIAG && noise_kind != TDA_NOISE_DENSE && !(noise_kind == TDA_NOISE_ADAPTIVE && e->nlev > 1))
     return fail(TDA_ERR_UNSUPPORTED, "noise kind %d (AdaptiveGaussianLogLike only below the finest level of a hierarchy)", noise_kind);
   HIP_TRY(hipSetDevice(e->cfg.device));
   Level& lv = e->levels[level];
@@ -316,11 +319,15 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
     lv.ufn_mala = nullptr;
     lv.ufn_mala_grad0 = nullptr;
   }
-  int rc = compile_user_model(source, &lv.umod, &lv.ufn, &lv.ufn_eval, &lv.ufn_level);
+  int rc = compile_user_model(source, loglike, &lv.umod, &lv.ufn, &lv.ufn_eval, &lv.ufn_level);
   if (rc) return rc;
   lv.usrc = source;
   std::vector<double> y(data, data + m), w;
-  if (noise_kind == TDA_NOISE_ADAPTIVE) {
+  lv.upar.release();
+  if (loglike) {
+    lv.var = 1.0;
+    if ((rc = lv.upar.upload(std::vector<double>(noise, noise + m)))) return rc;
+  } else if (noise_kind == TDA_NOISE_ADAPTIVE) {
     if ((rc = ext_level_adaptive(e, lv, m, data, noise))) return rc;
   } else if (noise_kind == TDA_NOISE_DENSE) {
     if ((rc = ext_level_dense(e, lv, m, noise))) return rc;
@@ -362,6 +369,8 @@ int tda_engine_set_level_callback(tda_engine* e, int level, tda_forward_batch_fn
   if (!e || !fn || !data || !noise) return fail(TDA_ERR_INVALID, "null argument");
   if (level < 0 || level >= (int)e->levels.size()) return fail(TDA_ERR_INVALID, "level %d out of range", level);
   if (m < 1) return fail(TDA_ERR_INVALID, "m must be >= 1");
+  if (noise_kind == TDA_NOISE_SOURCE)
+    return fail(TDA_ERR_UNSUPPORTED, "a source-defined likelihood (TDA_NOISE_SOURCE) needs a source-defined forward model (tda_engine_set_level_source)");
   if (noise_kind != TDA_NOISE_ISO && noise_kind != TDA_NOISE_DIAG && noise_kind != TDA_NOISE_DENSE && !(noise_kind == TDA_NOISE_ADAPTIVE && e->nlev > 1))
     return fail(TDA_ERR_UNSUPPORTED, "noise kind %d (AdaptiveGaussianLogLike only below the finest level of a hierarchy)", noise_kind);
   HIP_TRY(hipSetDevice(e->cfg.device));

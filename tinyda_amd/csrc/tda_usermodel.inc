@@ -23,7 +23,7 @@ struct UserStepArgs {
   const double* inc;
   const double* u;
   const double* data;
-  const double* w;  // 1 / diag(noise) or null (isotropic)
+  const double* w;  // 1 / diag(noise) or null (isotropic); source-defined likelihood: its per-output parameters
   double var;
   const double* pr_mean;
   const double* pr_pinv;
@@ -68,7 +68,25 @@ const char* const kUserPrelude = R"SRC(
 __device__ double tda_forward(const double* theta, int dim, int o);
 )SRC";
 
+// Source-defined likelihood (TDA_NOISE_SOURCE): log L(F) = sum_o tda_loglike_term(F_o, y_o, p_o, o), the function defined by the
+// source after tda_forward.  This prelude goes ahead of the user source and switches the kernels' likelihood over; the
+// Gaussian kinds compile without it, so their programs are what they were.  As with tda_gradient, a missing function
+// resolves to a tagged template that a static_assert names.  The args' `w` then carries p (not inverted).
+const char* const kLogLikePrelude = R"SRC(
+#define TDA_LOGLIKE_SOURCE 1
+struct tda_loglike_term_missing {};
+template <class O>
+__device__ tda_loglike_term_missing tda_loglike_term(double, double, double, O) { return {}; }
+struct tda_loglike_term_grad_missing {};
+template <class O>
+__device__ tda_loglike_term_grad_missing tda_loglike_term_grad(double, double, double, O) { return {}; }
+)SRC";
+
 const char* const kUserKernel = R"SRC(
+#ifdef TDA_LOGLIKE_SOURCE
+static_assert(!__is_same(decltype(tda_loglike_term(0.0, 0.0, 0.0, 0)), tda_loglike_term_missing),
+              "tda_loglike_term_missing: a source-defined likelihood needs __device__ double tda_loglike_term(double f, double y, double p, int o)");
+#endif
 struct UserStepArgs {
   long long N, NP;
   int d, DP, m, S, mode, prop_kind;
@@ -126,6 +144,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
     s_th[lane] = prp;
     s_th[lane2] = prp2;
     __syncthreads();
+#ifdef TDA_LOGLIKE_SOURCE
+    double sse = 0.0;  // source-defined likelihood: the sum of its terms, a.w = the per-output parameters (link.py:48 takes any loglike)
+    for (int o = lane; o < a.m; o += 64) sse += tda_loglike_term(tda_forward(s_th, a.d, o), a.data[o], a.w[o], o);
+    sse = tda_wave_sum(sse);
+#else
     double sse = 0.0;  // posterior.py:95-108, distributions.py:295-326
     for (int o = lane; o < a.m; o += 64) {
       const double r = tda_forward(s_th, a.d, o) - a.data[o];
@@ -134,6 +157,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
       sse += sq;
     }
     sse = tda_wave_sum(sse);
+#endif
     const double dv = prp - pm;
     double pj = lj ? dv * dv * pinv : 0.0;
     if (a.pr_lo && lj && (prp < a.pr_lo[lane] || prp > a.pr_hi[lane])) pj = __builtin_inf();  // uniform prior components
@@ -143,7 +167,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
       if (a.pr_lo && (prp2 < a.pr_lo[lane2] || prp2 > a.pr_hi[lane2])) pj = __builtin_inf();
     }
     const double maha = tda_wave_sum(pj);
+#ifdef TDA_LOGLIKE_SOURCE
+    const double ll_n = sse;
+#else
     const double ll_n = a.w ? -0.5 * sse : -0.5 * sse / a.var;
+#endif
     const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
     const double post_n = lp_n + ll_n;               // link.py:48
     bool acc = true;
@@ -221,6 +249,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_level_action(const Use
   s_th[lane] = yj;
   s_th[lane2] = yj2;
   __syncthreads();
+#ifdef TDA_LOGLIKE_SOURCE
+  double lls = 0.0;  // source-defined likelihood: a.w = the per-output parameters
+  for (int o = lane; o < a.m; o += 64) lls += tda_loglike_term(tda_forward(s_th, a.d, o), a.data[o], a.w[o], o);
+  const double lln = tda_wave_sum(lls);
+#else
   double sse = 0.0;
   for (int o = lane; o < a.m; o += 64) {
     const double r = tda_forward(s_th, a.d, o) - a.data[o];
@@ -230,6 +263,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_level_action(const Use
   }
   sse = tda_wave_sum(sse);
   const double lln = a.w ? -0.5 * sse : -0.5 * sse / a.var;
+#endif
   const double y_lp = ys ? ys[a.DP] : a.lp[(size_t)k * a.NP + c], y_ll = ys ? ys[a.DP + 1] : a.ll[(size_t)k * a.NP + c];
   const double x_lp = a.lp[(size_t)q * a.NP + c], x_ll = a.ll[(size_t)q * a.NP + c];
   const int pkq = q * (q - 1) / 2 + k;
@@ -331,6 +365,12 @@ __device__ tda_gradient_missing tda_gradient(const double*, int, const double*, 
 const char* const kMalaKernel = R"SRC(
 static_assert(!__is_same(decltype(tda_gradient((const double*)nullptr, 0, (const double*)nullptr, 0, 0)), tda_gradient_missing),
               "tda_gradient_missing: MALA needs __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)");
+#ifdef TDA_LOGLIKE_SOURCE
+static_assert(!__is_same(decltype(tda_loglike_term(0.0, 0.0, 0.0, 0)), tda_loglike_term_missing),
+              "tda_loglike_term_missing: a source-defined likelihood needs __device__ double tda_loglike_term(double f, double y, double p, int o)");
+static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_loglike_term_grad_missing),
+              "tda_loglike_term_grad_missing: MALA needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o)");
+#endif
 struct UserMalaArgs {
   long long N, NP;
   int d, DP, m, S;
@@ -359,6 +399,16 @@ __device__ __forceinline__ double tda_wave_sum(double v) {
 // outputs of the model at the parameters in s_th: returns this lane's share of the weighted sum of squares and leaves the
 // sensitivity grad_loglike = Sigma^-1 (y - F) in s_sens (distributions.py:300-301 iso: 1 / var * r, :314-315 diag: w * r)
 __device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, int lane) {
+#ifdef TDA_LOGLIKE_SOURCE
+  // source-defined likelihood: this lane's share of the log-likelihood itself, and d term / d f as the sensitivity
+  double lls = 0.0;
+  for (int o = lane; o < a.m; o += 64) {
+    const double f = tda_forward(s_th, a.d, o);
+    lls += tda_loglike_term(f, a.data[o], a.w[o], o);
+    s_sens[o] = tda_loglike_term_grad(f, a.data[o], a.w[o], o);
+  }
+  return lls;
+#else
   const double iv = 1.0 / a.var;
   double sse = 0.0;
   for (int o = lane; o < a.m; o += 64) {
@@ -370,6 +420,7 @@ __device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const 
     s_sens[o] = (a.w ? a.w[o] : iv) * (a.data[o] - f);
   }
   return sse;
+#endif
 }
 // one wave per chain: lane j owns parameter j (and j + 64 at 65 .. 128 parameters), the lanes stride over the outputs
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
@@ -406,7 +457,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
       pj += dv2 * dv2 * pinv2;
     }
     const double maha = tda_wave_sum(pj);
+#ifdef TDA_LOGLIKE_SOURCE
+    const double ll_n = sse;
+#else
     const double ll_n = a.w ? -0.5 * sse : -0.5 * sse / a.var;
+#endif
     const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
     const double post_n = lp_n + ll_n;               // link.py:48
     __syncthreads();  // s_sens complete
@@ -499,12 +554,14 @@ int hiprtc_gfx950(const std::string& src, const char* name, std::vector<char>& c
 }
 
 // compile prelude + user source + kernel for gfx950; on failure the hiprtc log goes into the error message
-int compile_user_model(const char* source, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_eval, hipFunction_t* fn_level) {
-  std::string src = std::string(kUserPrelude) + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kUserKernel;
+int compile_user_model(const char* source, bool loglike, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_eval, hipFunction_t* fn_level) {
+  std::string src = std::string(kUserPrelude) + (loglike ? kLogLikePrelude : "") + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kUserKernel;
   std::vector<char> code;
   std::string log;
   if (int rc = hiprtc_gfx950(src, "tda_user_model.hip", code, log)) return rc;
   if (code.empty()) {
+    if (log.find("tda_loglike_term_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "a source-defined likelihood: the source defines no __device__ double tda_loglike_term(double f, double y, double p, int o)");
     if (log.size() > 400) log.resize(400);
     return fail(TDA_ERR_INVALID, "the forward-model source does not compile: %s", log.c_str());
   }
@@ -517,8 +574,8 @@ int compile_user_model(const char* source, hipModule_t* mod, hipFunction_t* fn, 
 
 // the MALA program: prelude + user source + MALA kernels.  A source without tda_gradient resolves the kernels' call to the
 // tagged fallback template of the prelude, which a static_assert turns into the message below (not an unresolved symbol at load).
-int compile_user_mala(const std::string& source, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_grad0) {
-  std::string src = std::string(kUserPrelude) + kMalaPrelude + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kMalaKernel;
+int compile_user_mala(const std::string& source, bool loglike, hipModule_t* mod, hipFunction_t* fn, hipFunction_t* fn_grad0) {
+  std::string src = std::string(kUserPrelude) + kMalaPrelude + (loglike ? kLogLikePrelude : "") + "\n// ---- user source ----\n" + source + "\n// ---- engine ----\n" + kMalaKernel;
   std::vector<char> code;
   std::string log;
   if (int rc = hiprtc_gfx950(src, "tda_user_mala.hip", code, log)) return rc;
@@ -526,6 +583,9 @@ int compile_user_mala(const std::string& source, hipModule_t* mod, hipFunction_t
     if (log.find("tda_gradient_missing") != std::string::npos)
       return fail(TDA_ERR_INVALID, "MALA on a source-defined model: the source defines no __device__ double tda_gradient(const double* theta, "
                                    "int dim, const double* sensitivity, int n_outputs, int j)");
+    if (log.find("tda_loglike_term_grad_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "MALA with a source-defined likelihood: the source defines no __device__ double tda_loglike_term_grad(double f, "
+                                   "double y, double p, int o)");
     if (log.size() > 400) log.resize(400);
     return fail(TDA_ERR_INVALID, "the forward-model source does not compile with the MALA kernels: %s", log.c_str());
   }

@@ -132,9 +132,12 @@ class Engine:
         self._ck(self.lib.tda_engine_set_prior_joint(self.h, _ptr(kinds), _ptr(loc), _ptr(scale)))
 
     def set_level_source(self, level, source, data, noise_kind, noise):
-        """forward model as HIP source defining `__device__ double tda_forward(const double* theta, int dim, int o)`"""
+        """forward model as HIP source defining `__device__ double tda_forward(const double* theta, int dim, int o)`;
+        noise_kind 4 (_lib.NOISE_SOURCE): the source also defines `tda_loglike_term`, `noise` holds its per-output parameters"""
         data = _f64(np.atleast_1d(data))
         noise = _f64(np.atleast_1d(noise))
+        if noise_kind == _lib.NOISE_SOURCE and noise.shape != data.shape:
+            raise ValueError("a source-defined likelihood takes one parameter per model output")
         self._ck(self.lib.tda_engine_set_level_source(self.h, level, source.encode(), data.size, _ptr(data), noise_kind, _ptr(noise)))
 
     def set_level_callback(self, level, fn, data, noise_kind, noise, inplace=False):

@@ -3,10 +3,14 @@
 All are *unnormalised* (-1/2 r^T Sigma^-1 r).  `GaussianLogLike` is the reference's factory: a diagonal
 covariance with equal entries becomes isotropic, a diagonal one diagonal, anything else dense
 (distributions.py:237-243).  Each class also reports how the device engine should see it (`_lowering`).
+`DeviceLogLike` (extension) is a separable log-likelihood given as HIP source, for everything that is not Gaussian.
 """
+import re
+
 import numpy as np
 
 from . import _lib
+from .models import _strip_comments
 
 
 def _check_covariance(data, covariance):
@@ -106,6 +110,53 @@ def GaussianLogLike(data, covariance):
             return IsotropicGaussianLogLike(data, covariance[0, 0])
         return DiagonalGaussianLogLike(data, covariance)
     return DefaultGaussianLogLike(data, covariance)
+
+
+class DeviceLogLike:
+    """A separable log-likelihood given as HIP source (extension; the reference takes any object with `loglike`,
+    posterior.py:95-108, and evaluates it in Python): log L(F) = sum_o term(F_o, y_o, p_o, o).  The source must define
+
+        __device__ double tda_loglike_term(double f, double y, double p, int o);        // term o
+
+    and may define its derivative with respect to the model output, which MALA needs as the sensitivity:
+
+        __device__ double tda_loglike_term_grad(double f, double y, double p, int o);   // d term / d f
+
+    `data` is y, `parameters` one value per output (a scale, an exposure, a censoring limit; ones when not given);
+    constants shared by all outputs are literals in the source.  The functions are pure.  A term that is NaN or -inf
+    rejects the proposal.  Likelihoods that couple outputs are not covered.  It is compiled into the program of the
+    level's `DeviceModel`, so it lowers beside such a model only.
+
+    `reference(x, data, parameters)`, if given, returns the vector of terms in NumPy and serves `loglike` on the host
+    (host protocol, tests); `reference_gradient(x, data, parameters)` the vector of derivatives, which becomes
+    `grad_loglike` (an attribute only then, so that the host MALA takes the exact-gradient branch)."""
+
+    def __init__(self, source, data, parameters=None, reference=None, reference_gradient=None):
+        self.source = str(source)
+        self.data = np.atleast_1d(np.asarray(data, dtype=np.float64))
+        self.parameters = (np.ones_like(self.data) if parameters is None
+                           else np.atleast_1d(np.asarray(parameters, dtype=np.float64)))
+        if self.data.ndim != 1 or self.parameters.shape != self.data.shape:
+            raise ValueError("data and parameters must be vectors with one entry per model output")
+        stripped = _strip_comments(self.source)
+        if not re.search(r"\btda_loglike_term\s*\(", stripped):
+            raise ValueError("the source must define __device__ double tda_loglike_term(double f, double y, double p, int o)")
+        self.has_gradient = re.search(r"\btda_loglike_term_grad\s*\(", stripped) is not None
+        self.reference = reference
+        self.reference_gradient = reference_gradient
+        if reference_gradient is not None:
+            self.grad_loglike = self._reference_gradient  # (an attribute only then: MALA.setup_proposal looks for it)
+
+    def loglike(self, x):
+        if self.reference is None:
+            raise TypeError("this DeviceLogLike has no host reference implementation; run it with backend='hip'")
+        return np.sum(self.reference(np.asarray(x, dtype=np.float64), self.data, self.parameters))
+
+    def _reference_gradient(self, x):
+        return np.asarray(self.reference_gradient(np.asarray(x, dtype=np.float64), self.data, self.parameters), dtype=np.float64)
+
+    def _lowering(self):
+        return _lib.NOISE_SOURCE, self.parameters
 
 
 class JointPrior:

@@ -1,6 +1,7 @@
 """Posterior = prior x likelihood x forward model (tinyDA/posterior.py:41-151)."""
 import numpy as np
 
+from . import _lib
 from .records import Link
 from .models import BatchedModel, DeviceModel, LinearModel, Rosenbrock
 
@@ -78,8 +79,12 @@ class Posterior:
             data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
             if data.shape != (self.model.n_outputs,):
                 return None
-            return dict(prior_mean=mean, prior_cov=cov, source=self.model.source, has_gradient=self.model.has_gradient, A=None, b=None,
-                        data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
+            low = dict(prior_mean=mean, prior_cov=cov, source=self.model.source, has_gradient=self.model.has_gradient, A=None, b=None,
+                       data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
+            if kind == _lib.NOISE_SOURCE:  # DeviceLogLike: its functions are compiled with the model, one program
+                low.update(source=self.model.source + "\n" + self.likelihood.source, loglike_source=True,
+                           loglike_has_gradient=self.likelihood.has_gradient)
+            return low
         if isinstance(self.model, BatchedModel):
             kind, noise = self.likelihood._lowering()
             data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
