@@ -284,26 +284,21 @@ def test_oracle_level_gradient_against_differences():
             np.testing.assert_allclose(g[:, j], ((lp1 + ll1) - (lp0 + ll0)) / 2e-6, rtol=1e-6, atol=1e-7)
 
 
-# ---- 5. the hiprtc programs, assembled as the engine assembles them and compiled offline --------------------------------------
+# ---- 5. the hiprtc programs: the shipped file compiled offline as it stands, with the options the engine passes ---------------
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+CSRC = os.path.join(ROOT, "tinyda_amd", "csrc")
+PROGRAM = os.path.join(CSRC, "tda_user_program.hip")
 
 
-def _program_strings():
-    txt = open(os.path.join(ROOT, "tinyda_amd", "csrc", "tda_usermodel.inc")).read()
-    return dict(re.findall(r'const char\* const (\w+) = R"SRC\((.*?)\)SRC";', txt, flags=re.S))
-
-
-def _assemble(S, user_source, loglike, mala):
-    """compile_user_model / compile_user_mala of tda_usermodel.inc"""
-    return (S["kUserPrelude"] + (S["kMalaPrelude"] if mala else "") + (S["kLogLikePrelude"] if loglike else "")
-            + "\n// ---- user source ----\n" + user_source + "\n// ---- engine ----\n" + (S["kMalaKernel"] if mala else S["kUserKernel"]))
-
-
-def _compile(tmp_path, name, src):
-    path = tmp_path / (name + ".hip")
-    path.write_text(src)
+def _compile(tmp_path, name, user_source, loglike, mala):
+    """compile_user_program of tda_usermodel.inc: the user's source is the header tda_user_source.h, the switches are -D options"""
+    inc = tmp_path / name
+    inc.mkdir()
+    (inc / "tda_user_source.h").write_text(user_source)
+    switches = (["-DTDA_LOGLIKE_SOURCE"] if loglike else []) + (["-DTDA_USER_MALA"] if mala else [])
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-ffp-contract=off", "-std=c++17", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", str(path), "-o", str(tmp_path / (name + ".out"))],
+                        "-Rpass-analysis=kernel-resource-usage", "-I" + str(inc), "-I" + CSRC] + switches
+                       + [PROGRAM, "-o", str(tmp_path / (name + ".out"))],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     usage, fn = {}, None
     for ln in r.stdout.splitlines():
@@ -334,11 +329,10 @@ PROGRAMS = {  # name -> (likelihood kind or None for the Gaussian program, MALA 
 @pytest.mark.parametrize("name", list(PROGRAMS))
 def test_programs_compile_for_gfx950_without_scratch(tmp_path, name):
     kind, mala, kernels = PROGRAMS[name]
-    S = _program_strings()
     user = source() + (xl.KINDS[kind][0] if kind else "")
-    rc, log, usage = _compile(tmp_path, name, _assemble(S, user, kind is not None, mala))
+    rc, log, usage = _compile(tmp_path, name, user, kind is not None, mala)
     assert rc == 0, log[-3000:]
-    assert set(kernels) <= set(usage), (usage, log[-2000:])
+    assert set(kernels) == set(usage), (usage, log[-2000:])  # (each program holds exactly its own kernels)
     for k in kernels:
         print(name, k, usage[k])  # (scalar spills into vector lanes are reported, not asserted)
         assert usage[k]["ScratchSize [bytes/lane]"] == 0 and usage[k]["VGPRs Spill"] == 0, (k, usage[k])
@@ -346,23 +340,28 @@ def test_programs_compile_for_gfx950_without_scratch(tmp_path, name):
 
 @needs_hipcc
 def test_missing_functions_fail_with_a_message_naming_the_signature(tmp_path):
-    S = _program_strings()
-    rc, log, _ = _compile(tmp_path, "no_term", _assemble(S, source(), True, False))
+    rc, log, _ = _compile(tmp_path, "no_term", source(), True, False)
     assert rc != 0 and "tda_loglike_term_missing" in log
     assert "__device__ double tda_loglike_term(double f, double y, double p, int o)" in log
-    rc, log, _ = _compile(tmp_path, "no_term_mala", _assemble(S, source(), True, True))
+    rc, log, _ = _compile(tmp_path, "no_term_mala", source(), True, True)
     assert rc != 0 and "tda_loglike_term_missing" in log
-    rc, log, _ = _compile(tmp_path, "no_grad", _assemble(S, source() + xl.TERM_ONLY_SRC, True, True))
+    rc, log, _ = _compile(tmp_path, "no_grad", source() + xl.TERM_ONLY_SRC, True, True)
     assert rc != 0 and "tda_loglike_term_grad_missing" in log and "tda_loglike_term_missing" not in log
     assert "__device__ double tda_loglike_term_grad(double f, double y, double p, int o)" in log
     # the same source serves the step program, which needs no derivative
-    rc, log, _ = _compile(tmp_path, "term_only_steps", _assemble(S, source() + xl.TERM_ONLY_SRC, True, False))
+    rc, log, _ = _compile(tmp_path, "term_only_steps", source() + xl.TERM_ONLY_SRC, True, False)
     assert rc == 0, log[-2000:]
 
 
 def test_gaussian_program_text_is_free_of_the_likelihood_switch():
-    """kinds 0-3 are compiled without the prelude: after preprocessing their programs are what they were"""
-    S = _program_strings()
-    assert "#define TDA_LOGLIKE_SOURCE" in S["kLogLikePrelude"]
-    for k in ("kUserPrelude", "kMalaPrelude", "kUserKernel", "kMalaKernel"):
-        assert "#define TDA_LOGLIKE_SOURCE" not in S[k]
+    """kinds 0-3 are compiled without the switch: after preprocessing their programs are what they were.  The program file and
+    the header it includes never define TDA_LOGLIKE_SOURCE, and the one place in the host code that builds the option list
+    passes it for TDA_NOISE_SOURCE only."""
+    for f in ("tda_user_program.hip", "tda_user_args.h"):
+        txt = open(os.path.join(CSRC, f)).read()
+        assert not re.search(r"#\s*(define|undef)\s+TDA_LOGLIKE_SOURCE", txt), f
+    assert "#ifdef TDA_LOGLIKE_SOURCE" in open(PROGRAM).read()
+    host = open(os.path.join(CSRC, "tda_usermodel.inc")).read()  # (the only file that talks to hiprtc)
+    assert host.count("hiprtcCompileProgram(") == 1
+    uses = [ln for ln in host.splitlines() if "TDA_LOGLIKE_SOURCE" in ln]
+    assert len(uses) == 1 and re.search(r"if\s*\(\s*noise_kind\s*==\s*TDA_NOISE_SOURCE\s*\).*\"-DTDA_LOGLIKE_SOURCE\"", uses[0]), uses

@@ -298,11 +298,9 @@ struct Level {
     if (cb_F_h) (void)hipHostFree(cb_F_h);
     cb_theta_h = cb_F_h = nullptr;
   }
-  hipModule_t umod = nullptr;
-  hipFunction_t ufn = nullptr, ufn_eval = nullptr, ufn_level = nullptr;
-  std::string usrc;                  // the model source (the MALA program is compiled from it at init)
-  hipModule_t umod_mala = nullptr;   // tda_user_mala_steps / tda_user_mala_grad0 (compile_user_mala)
-  hipFunction_t ufn_mala = nullptr, ufn_mala_grad0 = nullptr;
+  UserProgram uprog;       // tda_user_steps / tda_user_eval / tda_user_level_action
+  std::string usrc;        // the model source (the MALA program is compiled from it at init)
+  UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0
   DevBuf<double> udata, uw;
   DevBuf<double> upar;  // TDA_NOISE_SOURCE: the per-output parameters of the source's tda_loglike_term (as given, not inverted)
   double ros_a = 1.0, ros_b = 10.0, ros_data = 0.0;
@@ -970,16 +968,22 @@ void fill_level(const tda_engine* e, const Level& lv, StepArgs& a) {
 
 constexpr int MODEL_USER = 2;
 
+// what every kernel of a source-defined level takes: the sizes and the level's likelihood (UserStepArgs / UserLevelArgs / UserMalaArgs)
+template <class Args>
+void fill_user_level(const tda_engine* e, const Level& lv, Args& a) {
+  a.N = e->N;
+  a.NP = e->NP;
+  a.d = e->d;
+  a.DP = e->DP;
+  a.m = lv.m;
+  a.data = lv.udata.p;
+  a.w = lv.noise_kind == TDA_NOISE_SOURCE ? lv.upar.p : (lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr);
+  a.var = lv.var;
+}
+
 int fill_user_args(tda_engine* e, const Level& lv, UserStepArgs& ua) {
   if (e->prior_kind == PRIOR_DENSE) return fail(TDA_ERR_UNSUPPORTED, "source-defined forward models need a diagonal prior covariance");
-  ua.N = e->N;
-  ua.NP = e->NP;
-  ua.d = e->d;
-  ua.DP = e->DP;
-  ua.m = lv.m;
-  ua.data = lv.udata.p;
-  ua.w = lv.noise_kind == TDA_NOISE_SOURCE ? lv.upar.p : (lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr);
-  ua.var = lv.var;
+  fill_user_level(e, lv, ua);
   ua.pr_mean = e->prior_mean.p;
   ua.pr_pinv = e->prior_pinv.p;
   ua.pr_lo = e->prior_bounded ? e->prior_lo.p : nullptr;
@@ -991,20 +995,13 @@ int fill_user_args(tda_engine* e, const Level& lv, UserStepArgs& ua) {
 // MALA over a source-defined model: everything but the block (S, inc, u, records)
 int fill_user_mala_args(tda_engine* e, const Level& lv, UserMalaArgs& ga) {
   if (e->prior_kind == PRIOR_DENSE) return fail(TDA_ERR_UNSUPPORTED, "source-defined forward models need a diagonal prior covariance");
-  ga.N = e->N;
-  ga.NP = e->NP;
-  ga.d = e->d;
-  ga.DP = e->DP;
-  ga.m = lv.m;
+  fill_user_level(e, lv, ga);
   ga.theta = e->theta.p;
   ga.lp = e->lp.p;
   ga.ll = e->ll.p;
   ga.grad = e->mala_grad.p;
   ga.scaling = e->scaling.p;
   ga.acc_count = e->acc_count.p;
-  ga.data = lv.udata.p;
-  ga.w = lv.noise_kind == TDA_NOISE_SOURCE ? lv.upar.p : (lv.noise_kind == TDA_NOISE_DIAG ? lv.uw.p : nullptr);
-  ga.var = lv.var;
   ga.pr_mean = e->prior_mean.p;
   ga.pr_pinv = e->prior_pinv.p;
   ga.logconst = e->prior_logconst;
@@ -1076,7 +1073,7 @@ int ext_level_dense(tda_engine* /*e*/, Level& lv, int m, const double* cov) {
 // F[N][m] <- model(prop[N][d]) of a level whose model lives outside the engine's kernels: a batched host callback (through
 // page-locked staging buffers, one synchronisation) or a source-defined model (tda_user_eval, stays on the stream)
 int ext_model_outputs(tda_engine* e, const Level& lv) {
-  if (lv.model == MODEL_USER) return launch_user_eval(lv.ufn_eval, e->N, e->d, lv.m, lv.cb_prop.p, lv.cb_F.p, e->stream);
+  if (lv.model == MODEL_USER) return launch_user_eval(lv.uprog.eval, e->N, e->d, lv.m, lv.cb_prop.p, lv.cb_F.p, e->stream);
   if (lv.model == MODEL_LINEAR) {
     if (lv.Apk.p) {  // on the matrix cores, every operator fragment serving a 16-chain tile
       DISPATCH_DPAD_W(e->DP, hipLaunchKernelGGL((k_linear_outputs<DPAD>), dim3((unsigned)(e->NP / 16)), dim3(256), 0, e->stream, (long long)e->N,
@@ -1134,7 +1131,7 @@ int launch_eval(tda_engine* e, int level, double* theta, double* lp, double* ll)
     ua.lp = lp;
     ua.ll = ll;
     ua.scaling = e->scaling.p;
-    return launch_user_steps(e->levels[level].ufn, ua, e->stream);
+    return launch_user(e->levels[level].uprog.steps, ua, 0, e->stream);
   }
   StepArgs a{};
   fill_level(e, e->levels[level], a);
@@ -1301,8 +1298,8 @@ void tda_engine_destroy(tda_engine* e) {
     (void)hipEventDestroy(t.b);
   }
   for (auto& lv : e->levels) {
-    if (lv.umod) (void)hipModuleUnload(lv.umod);
-    if (lv.umod_mala) (void)hipModuleUnload(lv.umod_mala);
+    lv.uprog.unload();
+    lv.uprog_mala.unload();
     lv.release_callback_buffers();
   }
   if (e->copy_stream) {

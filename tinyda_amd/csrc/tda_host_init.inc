@@ -245,9 +245,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   }
   const bool owcn = !e->is_dreamz && e->pp.kind == TDA_PROP_OWCN, mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA;
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;
-  if (user_mala && !e->levels[0].umod_mala) {  // the second program: GRW / pCN / AM engines never build it
+  if (user_mala && !e->levels[0].uprog_mala.mod) {  // the second program: GRW / pCN / AM engines never build it
     Level& l0 = e->levels[0];
-    if ((rc = compile_user_mala(l0.usrc, l0.noise_kind == TDA_NOISE_SOURCE, &l0.umod_mala, &l0.ufn_mala, &l0.ufn_mala_grad0))) return rc;
+    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, &l0.uprog_mala))) return rc;
   }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;
@@ -419,7 +419,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   if (user_mala) {
     UserMalaArgs ga{};
     if ((rc = fill_user_mala_args(e, e->levels[0], ga))) return rc;
-    if ((rc = launch_user_mala(e->levels[0].ufn_mala_grad0, ga, e->stream))) return rc;
+    if ((rc = launch_user(e->levels[0].uprog_mala.grad0, ga, user_mala_lds(ga), e->stream))) return rc;
   } else if (mala) {
     const int64_t nt = NP * DP;
     hipLaunchKernelGGL(k_mala_grad0, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, e->stream, NP, DP, e->mala_H.p, e->mala_c.p,

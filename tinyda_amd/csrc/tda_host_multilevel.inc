@@ -82,7 +82,7 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
       ua.ring = adaptive ? e->ml_ring.p : nullptr;
       ua.ring_P = e->ring_P;
       ua.ring_pos = rp;
-      if ((urc = launch_user_steps(e->levels[0].ufn, ua, e->stream))) return urc;
+      if ((urc = launch_user(e->levels[0].uprog.steps, ua, 0, e->stream))) return urc;
       rp += n;
       s += n;
       cc[0] += (int)n;
@@ -278,16 +278,9 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
                            (unsigned long long)e->cfg.seed, (long long)e->cfg.chain_offset, (long long)(e->done[q] + row[q]), q,
                            ma.u_rep[q] ? ma.u_rep[q] + (size_t)row[q] * N : nullptr, ul);
         UserLevelArgs ua{};
-        ua.N = N;
-        ua.NP = NP;
-        ua.d = d;
-        ua.DP = DP;
-        ua.m = lq.m;
+        fill_user_level(e, lq, ua);
         ua.nlev = nl;
         ua.q = q;
-        ua.data = lq.udata.p;
-        ua.w = lq.noise_kind == TDA_NOISE_SOURCE ? lq.upar.p : (lq.noise_kind == TDA_NOISE_DIAG ? lq.uw.p : nullptr);
-        ua.var = lq.var;
         ua.theta = e->ml_theta.p;
         ua.lp = e->ml_lp.p;
         ua.ll = e->ml_ll.p;
@@ -301,7 +294,7 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
         ua.ring_P = e->ring_P;
         ua.ring_pos = rp++;
         ua.ysnap = (e->randomize && k == 0) ? e->ml_ysnap.p : nullptr;
-        int lrc = launch_user_level(lq.ufn_level, ua, e->stream);
+        int lrc = launch_user(lq.uprog.level, ua, 0, e->stream);
         if (lrc) return lrc;
         cc[k] = 0;
         cc[q] += 1;

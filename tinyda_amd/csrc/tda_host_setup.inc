@@ -306,20 +306,9 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
     return fail(TDA_ERR_UNSUPPORTED, "noise kind %d (AdaptiveGaussianLogLike only below the finest level of a hierarchy)", noise_kind);
   HIP_TRY(hipSetDevice(e->cfg.device));
   Level& lv = e->levels[level];
-  if (lv.umod) {
-    (void)hipModuleUnload(lv.umod);
-    lv.umod = nullptr;
-    lv.ufn = nullptr;
-    lv.ufn_eval = nullptr;
-    lv.ufn_level = nullptr;
-  }
-  if (lv.umod_mala) {
-    (void)hipModuleUnload(lv.umod_mala);
-    lv.umod_mala = nullptr;
-    lv.ufn_mala = nullptr;
-    lv.ufn_mala_grad0 = nullptr;
-  }
-  int rc = compile_user_model(source, loglike, &lv.umod, &lv.ufn, &lv.ufn_eval, &lv.ufn_level);
+  lv.uprog.unload();
+  lv.uprog_mala.unload();
+  int rc = compile_user_program(source, noise_kind, false, &lv.uprog);
   if (rc) return rc;
   lv.usrc = source;
   std::vector<double> y(data, data + m), w;

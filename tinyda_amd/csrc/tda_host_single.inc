@@ -365,7 +365,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       ga.rec_stats = sa.rec_stats;
       ga.rec_acc = sa.rec_acc;
       ScopedTimer tm(e, 1);
-      if ((urc = launch_user_mala(lv.ufn_mala, ga, e->stream))) return urc;
+      if ((urc = launch_user(lv.uprog_mala.steps, ga, user_mala_lds(ga), e->stream))) return urc;
     } else if (lv.model == MODEL_USER) {
       UserStepArgs ua{};
       int urc = fill_user_args(e, lv, ua);
@@ -384,7 +384,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       ua.rec_stats = sa.rec_stats;
       ua.rec_acc = sa.rec_acc;
       ScopedTimer tm(e, 1);
-      if ((urc = launch_user_steps(lv.ufn, ua, e->stream))) return urc;
+      if ((urc = launch_user(lv.uprog.steps, ua, 0, e->stream))) return urc;
     } else {
       ScopedTimer tm(e, 1);
       DISPATCH_DPAD_W(e->DP, launch_steps<DPAD>(sa, NP / 16, lds, e->stream));

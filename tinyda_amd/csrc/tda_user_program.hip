@@ -1,0 +1,370 @@
+// The programs that hiprtc compiles at run time together with a user's HIP source (tda_usermodel.inc; embedded in the library as
+// text, and compiled offline as it stands by tests/test_loglike_source.py).  The user's source is the header "tda_user_source.h":
+//     __device__ double tda_forward(const double* theta, int dim, int o);     // output o of F(theta)
+// so that non-linear models run fused on the device instead of through the host protocol (the reference evaluates a Python
+// callable per chain and step, posterior.py:95-96).  One wave per chain: lane j owns parameter j (and j + 64 at 65 .. 128
+// parameters), the lanes stride over the outputs.  Same step semantics, records and RNG inputs as k_mh_steps; proposals,
+// adaptation and Cholesky stay the engine's own kernels.
+// Two compile options select what is built (the file itself never defines them):
+//   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
+//                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
+//     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
+//                         = (J(theta)^T sensitivity)_j (the reference's model.gradient(parameters, sensitivity), proposal.py:996-998)
+//   -DTDA_LOGLIKE_SOURCE  source-defined likelihood (TDA_NOISE_SOURCE): log L(F) = sum_o tda_loglike_term(F_o, y_o, p_o, o), defined
+//                         by the source after tda_forward; the args' `w` then carries p (not inverted).  MALA also needs
+//                         tda_loglike_term_grad, d term / d f.  The Gaussian kinds compile without it.
+#include <hip/hip_runtime.h>
+#include "tda_user_args.h"
+__device__ double tda_forward(const double* theta, int dim, int o);
+
+// Fallbacks a call resolves to when the source does not define a function of the contract's signature (a non-template function of
+// that signature wins overload resolution against them); the static_asserts below turn them into a message, not an unresolved
+// symbol at load.
+#ifdef TDA_USER_MALA
+struct tda_gradient_missing {};
+template <class J>
+__device__ tda_gradient_missing tda_gradient(const double*, int, const double*, int, J) { return {}; }
+#endif
+#ifdef TDA_LOGLIKE_SOURCE
+struct tda_loglike_term_missing {};
+template <class O>
+__device__ tda_loglike_term_missing tda_loglike_term(double, double, double, O) { return {}; }
+struct tda_loglike_term_grad_missing {};
+template <class O>
+__device__ tda_loglike_term_grad_missing tda_loglike_term_grad(double, double, double, O) { return {}; }
+#endif
+
+#include "tda_user_source.h"
+
+#ifdef TDA_USER_MALA
+static_assert(!__is_same(decltype(tda_gradient((const double*)nullptr, 0, (const double*)nullptr, 0, 0)), tda_gradient_missing),
+              "tda_gradient_missing: MALA needs __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)");
+#endif
+#ifdef TDA_LOGLIKE_SOURCE
+static_assert(!__is_same(decltype(tda_loglike_term(0.0, 0.0, 0.0, 0)), tda_loglike_term_missing),
+              "tda_loglike_term_missing: a source-defined likelihood needs __device__ double tda_loglike_term(double f, double y, double p, int o)");
+#ifdef TDA_USER_MALA
+static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_loglike_term_grad_missing),
+              "tda_loglike_term_grad_missing: MALA needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o)");
+#endif
+#endif
+
+__device__ __forceinline__ double tda_wave_sum(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// the log-likelihood from the wave's sum over the outputs: of the terms themselves (source-defined), or of the weighted squares
+// (posterior.py:95-108, distributions.py:295-326)
+__device__ __forceinline__ double tda_loglike_of_sum(double sum, const double* w, double var) {
+#ifdef TDA_LOGLIKE_SOURCE
+  (void)w, (void)var;
+  return sum;
+#else
+  return w ? -0.5 * sum : -0.5 * sum / var;
+#endif
+}
+
+#ifndef TDA_USER_MALA
+// log-likelihood of the model outputs at the parameters in s_th, for the whole wave (link.py:48 takes any loglike).  The level's
+// fields come in one by one: with the argument struct passed whole the kernels no longer compile to the instructions they had.
+__device__ __forceinline__ double tda_loglike(const double* s_th, int lane, int d, int m, const double* data, const double* w, double var) {
+  double sum = 0.0;
+#ifdef TDA_LOGLIKE_SOURCE
+  for (int o = lane; o < m; o += 64) sum += tda_loglike_term(tda_forward(s_th, d, o), data[o], w[o], o);
+#else
+  for (int o = lane; o < m; o += 64) {
+    const double r = tda_forward(s_th, d, o) - data[o];
+    double sq = r * r;
+    if (w) sq *= w[o];
+    sum += sq;
+  }
+#endif
+  return tda_loglike_of_sum(tda_wave_sum(sum), w, var);
+}
+extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepArgs a) {
+  __shared__ double s_th[128];  // (65 .. 128 parameters: a lane holds parameters `lane` and `lane + 64`)
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  double cur = lane < a.DP ? a.theta[c * a.DP + lane] : 0.0, cur2 = lane2 < a.DP ? a.theta[c * a.DP + lane2] : 0.0;
+  double lp = a.lp[c], ll = a.ll[c];
+  const double scal = a.scaling[c];
+  const bool pcn = a.prop_kind == 1, eval = a.mode == 1;
+  const double keep = pcn ? sqrt(1.0 - scal * scal) : 1.0;  // proposal.py:351-352
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+  int nacc = 0;
+  for (int s = 0; s < a.S; ++s) {
+    double prp = cur, prp2 = cur2;
+    if (!eval) {  // proposal.py:249-251 / :351-355
+      const double x = lane < a.DP ? a.inc[((size_t)s * a.NP + c) * a.DP + lane] : 0.0;
+      const double x2 = lane2 < a.DP ? a.inc[((size_t)s * a.NP + c) * a.DP + lane2] : 0.0;
+      const double sx = scal * x, sx2 = scal * x2;
+      prp = pcn ? keep * cur + sx : cur + sx;
+      prp2 = pcn ? keep * cur2 + sx2 : cur2 + sx2;
+    }
+    __syncthreads();
+    s_th[lane] = prp;
+    s_th[lane2] = prp2;
+    __syncthreads();
+    const double ll_n = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var);
+    const double dv = prp - pm;
+    double pj = lj ? dv * dv * pinv : 0.0;
+    if (a.pr_lo && lj && (prp < a.pr_lo[lane] || prp > a.pr_hi[lane])) pj = __builtin_inf();  // uniform prior components
+    if (lj2) {
+      const double dv2 = prp2 - pm2;
+      pj += dv2 * dv2 * pinv2;
+      if (a.pr_lo && (prp2 < a.pr_lo[lane2] || prp2 > a.pr_hi[lane2])) pj = __builtin_inf();
+    }
+    const double maha = tda_wave_sum(pj);
+    const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
+    const double post_n = lp_n + ll_n;               // link.py:48
+    bool acc = true;
+    if (!eval) {  // chain.py:112
+      const double delta = pcn ? ll_n - ll : post_n - (lp + ll);
+      double alpha = exp(delta);
+      if (post_n != post_n) alpha = 0.0;
+      acc = a.u[(size_t)s * a.NP + c] < alpha;
+    }
+    if (acc) {
+      lp = lp_n;
+      ll = ll_n;
+      cur = prp;
+      cur2 = prp2;
+    }
+    nacc += acc ? 1 : 0;
+    if (!eval) {
+      const size_t r = (size_t)s * a.N + c;
+      if (lane == 0) {
+        if (a.rec_stats) {
+          a.rec_stats[r * 3 + 0] = lp;
+          a.rec_stats[r * 3 + 1] = ll;
+          a.rec_stats[r * 3 + 2] = lp + ll;
+        }
+        if (a.rec_acc) a.rec_acc[r] = acc ? 1 : 0;
+        if (a.ring) a.ring[(size_t)((a.ring_pos + s) % a.ring_P) * a.NP + c] = acc ? 1 : 0;
+      }
+      if (a.rec_params && lj) a.rec_params[r * a.d + lane] = cur;
+      if (a.rec_params && lj2) a.rec_params[r * a.d + lane2] = cur2;
+    }
+  }
+  if (lane < a.DP) a.theta[c * a.DP + lane] = cur;
+  if (lane2 < a.DP) a.theta[c * a.DP + lane2] = cur2;
+  if (lane == 0) {
+    a.lp[c] = lp;
+    a.ll[c] = ll;
+    if (!eval && a.acc_count) a.acc_count[c] += nacc;
+    if (!eval && a.anyacc && nacc) a.anyacc[c] = 1;
+  }
+}
+// one step of level q >= 1 of a hierarchy (chain.py:353-402, :711-737; proposal.py:1515-1545), one wave per chain: the
+// same decision, alignment and records as the engine's k_ext_level_action, with the model evaluated in place
+extern "C" __global__ void __launch_bounds__(64) tda_user_level_action(const UserLevelArgs a) {
+  __shared__ double s_th[128];  // (65 .. 128 parameters: a second parameter per lane)
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const int q = a.q, k = a.q - 1;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const double* ys = a.ysnap ? a.ysnap + (size_t)c * (a.DP + 2) : nullptr;
+  double* thk = a.theta + ((size_t)k * a.NP + c) * a.DP;
+  double* thq = a.theta + ((size_t)q * a.NP + c) * a.DP;
+  const double yj = lj ? (ys ? ys[lane] : thk[lane]) : 0.0, xj = lj ? thq[lane] : 0.0;
+  const double yj2 = lj2 ? (ys ? ys[lane2] : thk[lane2]) : 0.0, xj2 = lj2 ? thq[lane2] : 0.0;
+  s_th[lane] = yj;
+  s_th[lane2] = yj2;
+  __syncthreads();
+  const double lln = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var);
+  const double y_lp = ys ? ys[a.DP] : a.lp[(size_t)k * a.NP + c], y_ll = ys ? ys[a.DP + 1] : a.ll[(size_t)k * a.NP + c];
+  const double x_lp = a.lp[(size_t)q * a.NP + c], x_ll = a.ll[(size_t)q * a.NP + c];
+  const int pkq = q * (q - 1) / 2 + k;
+  const double st_lp = a.Sst[((size_t)pkq * 2 + 0) * a.NP + c], st_ll = a.Sst[((size_t)pkq * 2 + 1) * a.NP + c];
+  const bool any = a.anyacc[(size_t)k * a.NP + c] != 0;
+  const double lpn = y_lp;
+  const double alpha = exp(((lpn + lln) - (x_lp + x_ll)) + (st_lp + st_ll) - (y_lp + y_ll));
+  const bool acc = any && (a.u[c] < alpha);
+  if (acc) {
+    if (lane < a.DP) thq[lane] = lj ? yj : 0.0;
+    if (lane2 < a.DP) thq[lane2] = lj2 ? yj2 : 0.0;
+    if (ys && lane < a.DP) thk[lane] = lj ? yj : 0.0;
+    if (ys && lane2 < a.DP) thk[lane2] = lj2 ? yj2 : 0.0;
+  } else {
+    for (int j = 0; j < q; ++j) {
+      if (lane < a.DP) a.theta[((size_t)j * a.NP + c) * a.DP + lane] = lj ? xj : 0.0;
+      if (lane2 < a.DP) a.theta[((size_t)j * a.NP + c) * a.DP + lane2] = lj2 ? xj2 : 0.0;
+    }
+  }
+  if (lane == 0) {
+    if (acc) {
+      a.lp[(size_t)q * a.NP + c] = lpn;
+      a.ll[(size_t)q * a.NP + c] = lln;
+      a.lp[(size_t)k * a.NP + c] = y_lp;
+      a.ll[(size_t)k * a.NP + c] = y_ll;
+    } else {
+      for (int j = 0; j < q; ++j) {
+        const int p = q * (q - 1) / 2 + j;
+        a.lp[(size_t)j * a.NP + c] = a.Sst[((size_t)p * 2 + 0) * a.NP + c];
+        a.ll[(size_t)j * a.NP + c] = a.Sst[((size_t)p * 2 + 1) * a.NP + c];
+      }
+    }
+    for (int j = 0; j < q; ++j)
+      for (int q2 = j + 1; q2 <= q; ++q2) {
+        const int p = q2 * (q2 - 1) / 2 + j;
+        a.Sst[((size_t)p * 2 + 0) * a.NP + c] = a.lp[(size_t)j * a.NP + c];
+        a.Sst[((size_t)p * 2 + 1) * a.NP + c] = a.ll[(size_t)j * a.NP + c];
+      }
+    a.anyacc[(size_t)k * a.NP + c] = 0;
+    if (q < a.nlev - 1 && acc) a.anyacc[(size_t)q * a.NP + c] = 1;
+    if (a.rec_stats) {
+      const double l1 = a.lp[(size_t)q * a.NP + c], l2 = a.ll[(size_t)q * a.NP + c];
+      a.rec_stats[c * 3 + 0] = l1;
+      a.rec_stats[c * 3 + 1] = l2;
+      a.rec_stats[c * 3 + 2] = l1 + l2;
+    }
+    if (a.rec_acc) a.rec_acc[c] = acc ? 1 : 0;
+    if (a.ring) a.ring[(size_t)(a.ring_pos % a.ring_P) * a.NP + c] = acc ? 1 : 0;
+  }
+  if (a.rec_params && lj) a.rec_params[c * a.d + lane] = acc ? yj : xj;
+  if (a.rec_params && lj2) a.rec_params[c * a.d + lane2] = acc ? yj2 : xj2;
+}
+// model outputs only, F[c][:] = F(prop[c][:]): the evaluation step of a hierarchy (Delayed Acceptance / MLDA), where the
+// engine's level kernels take the outputs from device memory exactly as they take a host callback's
+extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int d, int m, const double* prop, double* F) {
+  __shared__ double s_th[128];
+  const int lane = threadIdx.x;
+  const long long c = blockIdx.x;
+  if (c >= N) return;
+  s_th[lane] = lane < d ? prop[c * d + lane] : 0.0;
+  s_th[lane + 64] = lane + 64 < d ? prop[c * d + lane + 64] : 0.0;
+  __syncthreads();
+  for (int o = lane; o < m; o += 64) F[c * m + o] = tda_forward(s_th, d, o);
+}
+
+#else  // TDA_USER_MALA
+// outputs of the model at the parameters in s_th: returns this lane's share of the sum that tda_loglike_of_sum finishes (the
+// weighted squares, or the terms of a source-defined likelihood) and leaves the sensitivity in s_sens: grad_loglike =
+// Sigma^-1 (y - F) (distributions.py:300-301 iso: 1 / var * r, :314-315 diag: w * r), or d term / d f
+__device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, int lane) {
+  double sum = 0.0;
+#ifdef TDA_LOGLIKE_SOURCE
+  for (int o = lane; o < a.m; o += 64) {
+    const double f = tda_forward(s_th, a.d, o);
+    sum += tda_loglike_term(f, a.data[o], a.w[o], o);
+    s_sens[o] = tda_loglike_term_grad(f, a.data[o], a.w[o], o);
+  }
+#else
+  const double iv = 1.0 / a.var;
+  for (int o = lane; o < a.m; o += 64) {
+    const double f = tda_forward(s_th, a.d, o);
+    const double r = f - a.data[o];
+    double sq = r * r;
+    if (a.w) sq *= a.w[o];
+    sum += sq;
+    s_sens[o] = (a.w ? a.w[o] : iv) * (a.data[o] - f);
+  }
+#endif
+  return sum;
+}
+extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
+  extern __shared__ double s_sens[];  // [m]
+  __shared__ double s_th[128];
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const size_t row = (size_t)c * a.DP;
+  double cur = lj ? a.theta[row + lane] : 0.0, cur2 = lj2 ? a.theta[row + lane2] : 0.0;
+  double gc = lj ? a.grad[row + lane] : 0.0, gc2 = lj2 ? a.grad[row + lane2] : 0.0;  // gradient at the current state
+  double lp = a.lp[c], ll = a.ll[c];
+  const double sg = a.scaling[c], h = 0.5 * sg * sg, kq = -0.5 / (sg * sg);  // proposal.py:953, :1002
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+  int nacc = 0;
+  for (int s = 0; s < a.S; ++s) {
+    const double* z = a.inc + ((size_t)s * a.NP + c) * a.DP;
+    const double prp = lj ? (cur + h * gc) + sg * z[lane] : 0.0;  // proposal.py:951-956
+    const double prp2 = lj2 ? (cur2 + h * gc2) + sg * z[lane2] : 0.0;
+    __syncthreads();  // (the previous step's readers of s_th / s_sens are done)
+    s_th[lane] = prp;
+    s_th[lane2] = prp2;
+    __syncthreads();
+    const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, lane));
+    double pj = 0.0;
+    if (lj) {
+      const double dv = prp - pm;
+      pj = dv * dv * pinv;
+    }
+    if (lj2) {
+      const double dv2 = prp2 - pm2;
+      pj += dv2 * dv2 * pinv2;
+    }
+    const double maha = tda_wave_sum(pj);
+    const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);
+    const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
+    const double post_n = lp_n + ll_n;               // link.py:48
+    __syncthreads();  // s_sens complete
+    // gradient at the proposal: grad log prior + J^T grad loglike (proposal.py:996-998; utils.py:273-287)
+    const double gp = lj ? pinv * (pm - prp) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+    const double gp2 = lj2 ? pinv2 * (pm2 - prp2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+    // transition densities (proposal.py:1000-1005): q(x|y) = -|x - y - s^2/2 grad(y)|^2 / (2 s^2)
+    const double da = (cur - prp) - h * gp, da2 = (cur2 - prp2) - h * gp2;
+    const double db = (prp - cur) - h * gc, db2 = (prp2 - cur2) - h * gc2;
+    const double qa = tda_wave_sum(da * da + da2 * da2), qb = tda_wave_sum(db * db + db2 * db2);
+    double alpha = exp(((post_n - (lp + ll)) + kq * qa) - kq * qb);  // proposal.py:976-984
+    if (post_n != post_n) alpha = 0.0;
+    const bool acc = a.u[(size_t)s * a.NP + c] < alpha;  // chain.py:112
+    if (acc) {
+      lp = lp_n;
+      ll = ll_n;
+      cur = prp;
+      cur2 = prp2;
+      gc = gp;
+      gc2 = gp2;
+    }
+    nacc += acc ? 1 : 0;
+    const size_t r = (size_t)s * a.N + c;
+    if (lane == 0) {
+      if (a.rec_stats) {
+        a.rec_stats[r * 3 + 0] = lp;
+        a.rec_stats[r * 3 + 1] = ll;
+        a.rec_stats[r * 3 + 2] = lp + ll;
+      }
+      if (a.rec_acc) a.rec_acc[r] = acc ? 1 : 0;
+    }
+    if (a.rec_params && lj) a.rec_params[r * a.d + lane] = cur;
+    if (a.rec_params && lj2) a.rec_params[r * a.d + lane2] = cur2;
+  }
+  if (lane < a.DP) {
+    a.theta[row + lane] = cur;
+    a.grad[row + lane] = gc;
+  }
+  if (lane2 < a.DP) {
+    a.theta[row + lane2] = cur2;
+    a.grad[row + lane2] = gc2;
+  }
+  if (lane == 0) {
+    a.lp[c] = lp;
+    a.ll[c] = ll;
+    if (a.acc_count) a.acc_count[c] += nacc;
+  }
+}
+// gradient of the log-posterior at the current states (init; the padding of a row is written as zero)
+extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserMalaArgs a) {
+  extern __shared__ double s_sens[];
+  __shared__ double s_th[128];
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const size_t row = (size_t)c * a.DP;
+  const double th = lj ? a.theta[row + lane] : 0.0, th2 = lj2 ? a.theta[row + lane2] : 0.0;
+  s_th[lane] = th;
+  s_th[lane2] = th2;
+  __syncthreads();
+  (void)tda_mala_outputs(a, s_th, s_sens, lane);
+  __syncthreads();
+  if (lane < a.DP) a.grad[row + lane] = lj ? a.pr_pinv[lane] * (a.pr_mean[lane] - th) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? a.pr_pinv[lane2] * (a.pr_mean[lane2] - th2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+}
+#endif  // TDA_USER_MALA
