@@ -368,7 +368,24 @@ int tda_engine_set_state(tda_engine* e, const void* blob, int64_t bytes);
 /* JointPrior of independent scalar components (distributions.py:8-100) instead of a multivariate normal: kind[j] = 0 is
  * scipy.stats.norm(loc[j], scale[j]), kind[j] = 1 scipy.stats.uniform(loc[j], scale[j]) (density 1/scale on
  * [loc, loc + scale], log-density -inf outside: such proposals are rejected).  HOST arrays [dim].  Single-level chains,
- * GRW / AM, iso / diag noise (also with tda_engine_set_level_source); explicit initial parameters. */
+ * GRW / AM, iso / diag noise (also with tda_engine_set_level_source); explicit initial parameters.
+ * Source-defined prior (kind[j] = TDA_PRIOR_SOURCE for every j; the reference's JointPrior takes any scipy.stats.rv_continuous
+ * per parameter, distributions.py:8-56): the HIP source of every level (tda_engine_set_level_source) defines the terms of a
+ * separable log-prior log p(theta) = sum_j term(theta_j, p_j, q_j, j),
+ *     __device__ double tda_logprior_term(double x, double p, double q, int j);
+ * with p = loc[j] and q = scale[j], passed on as given (finite; q need not be positive).  The function is pure; the lane that
+ * owns parameter j calls it and the engine sums the terms.  A NaN or -inf term (a component outside its support) rejects the
+ * proposal; an initial state with such a term keeps it as its log-prior.  Components are either all of kind 0 / 1 or all
+ * source-defined: a mixture returns TDA_ERR_UNSUPPORTED.  The prior may be set before or after the levels: a level program
+ * compiled before the prior was set is compiled again by tda_engine_init (and by tda_engine_evaluate), where a source
+ * without tda_logprior_term returns TDA_ERR_INVALID naming the signature.  Evaluated inside tda_user_steps of the levels'
+ * programs only, so tda_engine_init refuses it with TDA_ERR_UNSUPPORTED wherever another kernel would evaluate the prior or the
+ * prior must be Gaussian: a level that is not source-defined or has dense noise, DREAM(Z), pCN, operator-weighted pCN, MALA,
+ * Independence, an error model, randomised subchain lengths, more than four levels; and with TDA_ERR_INVALID without explicit
+ * initial parameters.  What is lowered: single-level GRW / AM (dim up to 128; ISO / DIAG noise or TDA_NOISE_SOURCE) and
+ * Delayed Acceptance / MLDA of up to four such levels with fixed subchain lengths.  Checkpoint blobs do not record the prior
+ * (as for every prior): the restoring engine is configured like the saved one.  Priors that couple components are not covered. */
+enum { TDA_PRIOR_NORMAL = 0, TDA_PRIOR_UNIFORM = 1, TDA_PRIOR_SOURCE = 2 }; /* kind[j] of tda_engine_set_prior_joint */
 int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double* loc, const double* scale);
 
 /* Forward model given as HIP source (extension; the reference calls a Python callable per chain and step,

@@ -13,6 +13,7 @@ from .likelihoods import (  # noqa: F401
     AdaptiveGaussianLogLike,
     DefaultGaussianLogLike,
     DeviceLogLike,
+    DevicePrior,
     DiagonalGaussianLogLike,
     GaussianLogLike,
     IsotropicGaussianLogLike,

@@ -13,6 +13,7 @@ TDA_OK = 0
 TDA_ERR_INVALID, TDA_ERR_HIP, TDA_ERR_STATE, TDA_ERR_UNSUPPORTED, TDA_ERR_NUMERIC, TDA_ERR_CALLBACK = -1, -2, -3, -4, -5, -6
 NOISE_ISO, NOISE_DIAG, NOISE_DENSE, NOISE_ADAPTIVE = 0, 1, 2, 3
 NOISE_SOURCE = 4  # a separable log-likelihood in the level's HIP source (likelihoods.DeviceLogLike)
+PRIOR_NORMAL, PRIOR_UNIFORM, PRIOR_SOURCE = 0, 1, 2  # kinds of set_prior_joint; 2: tda_logprior_term in the levels' HIP source (likelihoods.DevicePrior)
 AEM_NONE, AEM_STATE_INDEPENDENT, AEM_STATE_DEPENDENT, AEM_STATE_INDEPENDENT_DIAGONAL = 0, 1, 2, 3
 PROP_GRW, PROP_PCN, PROP_AM, PROP_DREAMZ, PROP_INDEPENDENCE, PROP_OWCN, PROP_MALA = 0, 1, 2, 3, 4, 5, 6
 

@@ -70,6 +70,32 @@ def _loglike_source_refusal(low, n_levels, proposal, error_model, randomize):
     return None
 
 
+def _prior_source_refusal(low, n_levels, proposal, error_model, randomize):
+    """Why a posterior with a source-defined prior (DevicePrior, or a JointPrior of scipy families beyond norm / uniform) does
+    not lower (None when it does): the prior exists inside the step program compiled with a DeviceModel only, so every route
+    on which one of the engine's own kernels evaluates the prior, or which needs a Gaussian prior, is closed to it
+    (tda_engine_init refuses the same cases)."""
+    who = low["prior_source"]["label"]
+    if "source" not in low or low["noise_kind"] not in (_lib.NOISE_ISO, _lib.NOISE_DIAG, _lib.NOISE_SOURCE):
+        return ("%s is compiled into the programs of the levels' models, which must be DeviceModels with isotropic / diagonal noise "
+                "or a DeviceLogLike" % who)
+    if n_levels > MAX_LEVELS_FULL:
+        return "%s: hierarchies of at most %d levels" % (who, MAX_LEVELS_FULL)
+    if isinstance(proposal, DREAMZ):
+        return "%s is not lowered under DREAM(Z)" % who
+    if isinstance(proposal, (CrankNicolson, OperatorWeightedCrankNicolson)):
+        return "%s is not lowered under %s (it needs a Gaussian prior)" % (who, type(proposal).__name__)
+    if isinstance(proposal, MALA):
+        return "%s is not lowered under MALA" % who
+    if isinstance(proposal, IndependenceSampler):
+        return "%s is not lowered under IndependenceSampler" % who
+    if error_model is not None:
+        return "%s is not lowered together with an adaptive error model" % who
+    if randomize:
+        return "%s is not lowered with randomize_subchain_length" % who
+    return None
+
+
 def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=None, randomize=False):
     """Lowering pass: returns (list of level descriptions, proposal description) or None (the reason is left in _refusal).
     error_model: sample()'s adaptive_error_model after its own validation (None / 'state-independent' / 'state-dependent');
@@ -83,7 +109,11 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
     for post in posteriors:
         low = getattr(post, "_lowering", lambda: None)()
         if low is None or low["prior_mean"].shape[0] > MAX_PARAMETERS:
-            return _no("a posterior the engine cannot lower (an opaque Python model, a prior other than scipy's multivariate normal / JointPrior of norm and uniform, a likelihood outside GaussianLogLike's classes)" if low is None else "more than %d parameters" % MAX_PARAMETERS)
+            return _no("a posterior the engine cannot lower (an opaque Python model, a prior other than scipy's multivariate normal / JointPrior of the scipy families of csrc/tda_prior_families.h / DevicePrior, a likelihood outside GaussianLogLike's classes)" if low is None else "more than %d parameters" % MAX_PARAMETERS)
+        if "prior_source" in low:
+            why = _prior_source_refusal(low, len(posteriors), proposal, error_model, randomize)
+            if why is not None:
+                return _no(why)
         if low["noise_kind"] == _lib.NOISE_SOURCE:
             why = _loglike_source_refusal(low, len(posteriors), proposal, error_model, randomize)
             if why is not None:
@@ -184,7 +214,10 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
         if len(posteriors) != 1 or proposal._lowering() is None or "rosenbrock" in lows[0]:
             return _no("IndependenceSampler: single level, Gaussian q")
     for low in lows[1:]:  # one prior for the hierarchy (every tinyDA example shares it across levels)
-        if not (np.array_equal(low["prior_mean"], lows[0]["prior_mean"]) and np.array_equal(low["prior_cov"], lows[0]["prior_cov"])):
+        ps, ps0 = low.get("prior_source"), lows[0].get("prior_source")
+        same_source = (ps is None) == (ps0 is None) and (ps is None or (
+            ps["source"] == ps0["source"] and np.array_equal(ps["p"], ps0["p"]) and np.array_equal(ps["q"], ps0["q"])))
+        if not (np.array_equal(low["prior_mean"], lows[0]["prior_mean"]) and np.array_equal(low["prior_cov"], lows[0]["prior_cov"]) and same_source):
             return _no("the levels of a hierarchy must share one prior")
     prop = proposal._lowering()
     if prop is None:  # an option of a lowerable proposal class that the engine does not know: host protocol under 'auto'
@@ -228,6 +261,21 @@ def _host_rng(seed, tag, gid=None):
     by (seed, purpose, global chain id), so a seeded run is reproducible and does not depend on how chains are sharded
     over ranks; a shared archive (gid None) is keyed by (seed, purpose) alone, so every rank holds the same rows."""
     return np.random.default_rng([int(seed) & 0xFFFFFFFFFFFFFFFF, tag] + ([] if gid is None else [int(gid)]))
+
+
+def _source_prior_starts(prior, n_chains, chain_offset, seed):
+    """theta0 ~ prior (sampler.py:209) for a source-defined prior, drawn on the host from the prior's own components (DevicePrior:
+    from its reference): one row of uniforms per chain from the generator of the chain's global id, mapped through the
+    components' quantile functions, all chains of a component at once; a reference without `ppf` draws chain by chain from
+    `rvs(random_state=generator)`"""
+    rngs = [_host_rng(seed, _TAG_THETA0, chain_offset + c) for c in range(n_chains)]
+    host = getattr(prior, "reference", prior)
+    if hasattr(host, "ppf"):
+        d = prior.dim
+        return list(np.asarray(host.ppf(np.stack([r.random(d) for r in rngs])), dtype=np.float64).reshape(n_chains, d))
+    if not hasattr(host, "rvs"):
+        raise TypeError("this DevicePrior has no host reference implementation of ppf / rvs: sample() needs initial_parameters")
+    return [np.asarray(host.rvs(random_state=r), dtype=np.float64).reshape(prior.dim) for r in rngs]
 
 
 def _joint_rvs(joint, n, rng):
@@ -607,6 +655,8 @@ def _sample_device(plan, posterior, iterations, n_chains, initial_parameters, se
     try:
         if "prior_joint" in low:
             eng.set_prior_joint(*low["prior_joint"])
+            if initial_parameters is None and "prior_source" in low:
+                initial_parameters = _source_prior_starts(posterior.prior, n_chains, chain_offset, seed)
             if initial_parameters is None:  # sampler.py:209: theta0 ~ prior; uniform components are drawn on the host
                 initial_parameters = [_joint_rvs(low["prior_joint"], 1, _host_rng(seed, _TAG_THETA0, chain_offset + c))[0]
                                       for c in range(n_chains)]
@@ -702,6 +752,8 @@ def _sample_device_multilevel(plan, posteriors, iterations, n_chains, initial_pa
     try:
         if "prior_joint" in lows[0]:
             eng.set_prior_joint(*lows[0]["prior_joint"])
+            if initial_parameters is None and "prior_source" in lows[0]:
+                initial_parameters = _source_prior_starts(posteriors[0].prior, n_chains, chain_offset, seed)
         else:
             eng.set_prior(lows[0]["prior_mean"], lows[0]["prior_cov"])
         for k, low in enumerate(lows):

@@ -299,6 +299,7 @@ struct Level {
     cb_theta_h = cb_F_h = nullptr;
   }
   UserProgram uprog;       // tda_user_steps / tda_user_eval / tda_user_level_action
+  bool uprog_prior = false;  // uprog was compiled with -DTDA_PRIOR_SOURCE (ensure_user_programs rebuilds it when the prior changed since)
   std::string usrc;        // the model source (the MALA program is compiled from it at init)
   UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0
   DevBuf<double> udata, uw;
@@ -335,6 +336,7 @@ struct tda_engine {
   bool prior_is_standard = false;  // N(0, I): the single-level tile kernel skips the constant loads
   bool prior_bounded = false;      // JointPrior with uniform components: support bounds in prior_lo / prior_hi
   bool prior_joint = false;        // set by tda_engine_set_prior_joint (MALA over a source-defined model refuses it)
+  bool prior_source = false;       // TDA_PRIOR_SOURCE: tda_logprior_term of the levels' sources; prior_mean / prior_pinv hold its p / q
   double prior_logconst = 0.0;
   std::vector<double> prior_mean_h, prior_cov_h, prior_L_h;
   DevBuf<double> prior_lo, prior_hi;
@@ -1110,7 +1112,21 @@ int ext_step(tda_engine* e, const Level& lv, const ExtArgs& xa) {
   return TDA_OK;
 }
 
+// A source-defined prior lives in the levels' step programs: a program compiled before the prior was set (or after it changed)
+// is compiled again here, from the source the level keeps.  tda_engine_init and tda_engine_evaluate call this.
+int ensure_user_programs(tda_engine* e) {
+  for (Level& lv : e->levels) {
+    if (!lv.set || lv.model != MODEL_USER || lv.uprog_prior == e->prior_source) continue;
+    lv.uprog.unload();
+    if (int rc = compile_user_program(lv.usrc.c_str(), lv.noise_kind, false, e->prior_source, &lv.uprog)) return rc;
+    lv.uprog_prior = e->prior_source;
+  }
+  return TDA_OK;
+}
+
 int launch_eval(tda_engine* e, int level, double* theta, double* lp, double* ll) {
+  if (e->prior_source && (e->levels[level].model != MODEL_USER || e->levels[level].noise_kind == TDA_NOISE_DENSE))
+    return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior is evaluated by the step program of a source-defined model with isotropic / diagonal noise or a source-defined likelihood");
   if (e->levels[level].model == MODEL_CALLBACK || (e->levels[level].model == MODEL_USER && e->levels[level].noise_kind == TDA_NOISE_DENSE)) {
     ExtArgs xa{};
     fill_ext_args(e, e->levels[level], xa);

@@ -7,6 +7,23 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   if (!e->prior_set || !e->prop_set) return fail(TDA_ERR_STATE, "set_prior and set_proposal must precede init");
   for (auto& lv : e->levels)
     if (!lv.set) return fail(TDA_ERR_STATE, "set_level missing");
+  if (e->prior_source) {
+    // a source-defined prior (TDA_PRIOR_SOURCE) exists inside tda_user_steps of the levels' programs only: every route on which
+    // one of the engine's own kernels (k_ext_accept, k_mh_steps, k_ml_steps, k_da_steps, the DREAM(Z) kernels) would evaluate
+    // the prior, or that needs the prior to be Gaussian, would read p / q as a mean and an inverse variance
+    for (const Level& ls : e->levels)
+      if (ls.model != MODEL_USER || ls.noise_kind == TDA_NOISE_DENSE)
+        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior needs source-defined forward models with isotropic / diagonal noise or a source-defined likelihood at every level");
+    if (e->is_dreamz) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under DREAM(Z) is not lowered");
+    if (e->pp.kind == TDA_PROP_PCN || e->pp.kind == TDA_PROP_OWCN)
+      return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under pCN and operator-weighted pCN is not lowered (they need a Gaussian prior)");
+    if (e->pp.kind == TDA_PROP_MALA) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA is not lowered");
+    if (e->pp.kind == TDA_PROP_INDEPENDENCE) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under the Independence proposal is not lowered");
+    if (e->aem) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior together with an error model is not lowered");
+    if (e->nlev > 1 && e->randomize) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior with randomised subchain lengths is not lowered");
+    if (e->nlev > AEM_MAXLEV) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior: hierarchies of at most %d levels", (int)AEM_MAXLEV);
+    if (!theta0) return fail(TDA_ERR_INVALID, "a source-defined prior needs explicit initial parameters");
+  }
   if (e->nlev > AEM_MAXLEV) {  // five and six levels (0.5): the generic level kernel over the engine's own models, no error model
     if (e->aem) return fail(TDA_ERR_UNSUPPORTED, "error models are lowered for hierarchies of at most %d levels", (int)AEM_MAXLEV);
     if (e->wide) return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: hierarchies of at most %d levels", (int)AEM_MAXLEV);
@@ -99,6 +116,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   const int d = e->d, DP = e->DP;
   const int64_t N = e->N, NP = e->NP;
   int rc;
+  if ((rc = ensure_user_programs(e))) return rc;
   if ((rc = e->theta.alloc((size_t)NP * DP))) return rc;
   if ((rc = e->lp.alloc(NP))) return rc;
   if ((rc = e->ll.alloc(NP))) return rc;
@@ -247,7 +265,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;
   if (user_mala && !e->levels[0].uprog_mala.mod) {  // the second program: GRW / pCN / AM engines never build it
     Level& l0 = e->levels[0];
-    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, &l0.uprog_mala))) return rc;
+    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, false, &l0.uprog_mala))) return rc;
   }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;

@@ -222,6 +222,7 @@ int tda_engine_evaluate(tda_engine* e, int level, const double* theta, int64_t n
   if (n < 1 || n > e->N) return fail(TDA_ERR_INVALID, "n must be in 1..n_chains");
   HIP_TRY(hipSetDevice(e->cfg.device));
   int rc;
+  if ((rc = ensure_user_programs(e))) return rc;
   const int64_t NP = e->NP;
   if (!e->theta_s.p) {
     if ((rc = e->theta_s.alloc((size_t)NP * e->DP))) return rc;

@@ -52,6 +52,7 @@ int tda_engine_set_prior(tda_engine* e, const double* mean, const double* cov) {
   e->prior_logconst = d * std::log(2.0 * M_PI) + logdet;
   e->prior_bounded = false;
   e->prior_joint = false;
+  e->prior_source = false;
   e->prior_set = true;
   return TDA_OK;
 }
@@ -66,7 +67,21 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
   e->prior_L_h.assign((size_t)d * d, 0.0);
   double logconst = 0.0;
   bool bounded = false;
+  int n_source = 0;
+  for (int j = 0; j < d; ++j) n_source += kind[j] == TDA_PRIOR_SOURCE ? 1 : 0;
+  if (n_source && n_source != d)
+    return fail(TDA_ERR_UNSUPPORTED, "prior components are either all source-defined (kind %d) or all normal / uniform", (int)TDA_PRIOR_SOURCE);
   for (int j = 0; j < d; ++j) {
+    if (n_source) {
+      // tda_logprior_term(theta_j, p_j, q_j, j) of the levels' sources: p = loc, q = scale, passed on as given.  The host-side
+      // moments are placeholders (standard normal): every route that reads them is refused at tda_engine_init.
+      if (!std::isfinite(loc[j]) || !std::isfinite(scale[j])) return fail(TDA_ERR_NUMERIC, "prior component %d: p and q must be finite", j);
+      mh[j] = loc[j];
+      ph[j] = scale[j];
+      e->prior_cov_h[(size_t)j * d + j] = 1.0;
+      e->prior_L_h[(size_t)j * d + j] = 1.0;
+      continue;
+    }
     if (!(scale[j] > 0.0)) return fail(TDA_ERR_NUMERIC, "prior component %d: scale must be positive", j);
     if (kind[j] == 0) {  // scipy.stats.norm(loc, scale)
       mh[j] = loc[j];
@@ -84,7 +99,7 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
       e->prior_cov_h[(size_t)j * d + j] = scale[j] * scale[j] / 12.0;
       e->prior_L_h[(size_t)j * d + j] = scale[j] / std::sqrt(12.0);
     } else {
-      return fail(TDA_ERR_UNSUPPORTED, "prior component %d: kind %d (0 = normal, 1 = uniform)", j, (int)kind[j]);
+      return fail(TDA_ERR_UNSUPPORTED, "prior component %d: kind %d (0 = normal, 1 = uniform, 2 = source-defined)", j, (int)kind[j]);
     }
   }
   int rc;
@@ -96,6 +111,7 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
   e->prior_logconst = logconst;
   e->prior_bounded = bounded;
   e->prior_joint = true;
+  e->prior_source = n_source != 0;
   e->prior_set = true;
   return TDA_OK;
 }
@@ -308,8 +324,9 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
   Level& lv = e->levels[level];
   lv.uprog.unload();
   lv.uprog_mala.unload();
-  int rc = compile_user_program(source, noise_kind, false, &lv.uprog);
+  int rc = compile_user_program(source, noise_kind, false, e->prior_source, &lv.uprog);
   if (rc) return rc;
+  lv.uprog_prior = e->prior_source;  // (a prior set later: tda_engine_init compiles again, ensure_user_programs)
   lv.usrc = source;
   std::vector<double> y(data, data + m), w;
   lv.upar.release();

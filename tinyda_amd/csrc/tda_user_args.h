@@ -16,7 +16,7 @@ struct UserStepArgs {
   const double* data;
   const double* w;  // 1 / diag(noise) or null (isotropic); source-defined likelihood: its per-output parameters (not inverted)
   double var;
-  const double* pr_mean;
+  const double* pr_mean;  // diagonal Gaussian prior: mean and 1 / variance; source-defined prior: its p and q per parameter, as given
   const double* pr_pinv;
   const double* pr_lo;
   const double* pr_hi;

@@ -5,7 +5,7 @@
 // callable per chain and step, posterior.py:95-96).  One wave per chain: lane j owns parameter j (and j + 64 at 65 .. 128
 // parameters), the lanes stride over the outputs.  Same step semantics, records and RNG inputs as k_mh_steps; proposals,
 // adaptation and Cholesky stay the engine's own kernels.
-// Two compile options select what is built (the file itself never defines them):
+// Three compile options select what is built (the file itself never defines them):
 //   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
 //                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
 //     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
@@ -13,6 +13,9 @@
 //   -DTDA_LOGLIKE_SOURCE  source-defined likelihood (TDA_NOISE_SOURCE): log L(F) = sum_o tda_loglike_term(F_o, y_o, p_o, o), defined
 //                         by the source after tda_forward; the args' `w` then carries p (not inverted).  MALA also needs
 //                         tda_loglike_term_grad, d term / d f.  The Gaussian kinds compile without it.
+//   -DTDA_PRIOR_SOURCE    source-defined prior (tda_engine_set_prior_joint, kind TDA_PRIOR_SOURCE): log p(theta) = sum_j
+//                         tda_logprior_term(theta_j, p_j, q_j, j), defined by the source; the args' `pr_mean` / `pr_pinv` then carry
+//                         p / q as given.  tda_user_steps alone evaluates a prior; the MALA program does not take the switch.
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -33,6 +36,14 @@ struct tda_loglike_term_grad_missing {};
 template <class O>
 __device__ tda_loglike_term_grad_missing tda_loglike_term_grad(double, double, double, O) { return {}; }
 #endif
+#ifdef TDA_PRIOR_SOURCE
+#ifdef TDA_USER_MALA
+#error "TDA_PRIOR_SOURCE: the MALA program knows the diagonal Gaussian prior only"
+#endif
+struct tda_logprior_term_missing {};
+template <class J>
+__device__ tda_logprior_term_missing tda_logprior_term(double, double, double, J) { return {}; }
+#endif
 
 #include "tda_user_source.h"
 
@@ -47,6 +58,10 @@ static_assert(!__is_same(decltype(tda_loglike_term(0.0, 0.0, 0.0, 0)), tda_logli
 static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_loglike_term_grad_missing),
               "tda_loglike_term_grad_missing: MALA needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o)");
 #endif
+#endif
+#ifdef TDA_PRIOR_SOURCE
+static_assert(!__is_same(decltype(tda_logprior_term(0.0, 0.0, 0.0, 0)), tda_logprior_term_missing),
+              "tda_logprior_term_missing: a source-defined prior needs __device__ double tda_logprior_term(double x, double p, double q, int j)");
 #endif
 
 __device__ __forceinline__ double tda_wave_sum(double v) {
@@ -109,6 +124,12 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
     s_th[lane2] = prp2;
     __syncthreads();
     const double ll_n = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var);
+#ifdef TDA_PRIOR_SOURCE
+    // source-defined prior: the sum of the components' terms (pm / pinv hold p / q); a component outside its support is -inf
+    double pj = lj ? tda_logprior_term(prp, pm, pinv, lane) : 0.0;
+    if (lj2) pj += tda_logprior_term(prp2, pm2, pinv2, lane2);
+    const double lp_n = tda_wave_sum(pj);  // distributions.py:44-56 (JointPrior.logpdf)
+#else
     const double dv = prp - pm;
     double pj = lj ? dv * dv * pinv : 0.0;
     if (a.pr_lo && lj && (prp < a.pr_lo[lane] || prp > a.pr_hi[lane])) pj = __builtin_inf();  // uniform prior components
@@ -119,6 +140,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
     }
     const double maha = tda_wave_sum(pj);
     const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
+#endif
     const double post_n = lp_n + ll_n;               // link.py:48
     bool acc = true;
     if (!eval) {  // chain.py:112

@@ -35,7 +35,7 @@ struct UserProgram {
 // hiprtc for gfx950: tda_user_program.hip with the user's source and the argument structs as its named headers.  A source
 // without a function that the selected kernels call resolves to the program's tagged fallback template, which a static_assert
 // turns into the messages below (not an unresolved symbol at load); any other failure quotes the (truncated) compiler log.
-int compile_user_program(const char* source, int noise_kind, bool mala, UserProgram* out) {
+int compile_user_program(const char* source, int noise_kind, bool mala, bool prior_source, UserProgram* out) {
   const char* const headers[] = {source, tda_user_args_text};
   const char* const names[] = {"tda_user_source.h", "tda_user_args.h"};
   hiprtcProgram prog;
@@ -44,6 +44,7 @@ int compile_user_program(const char* source, int noise_kind, bool mala, UserProg
   std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   if (noise_kind == TDA_NOISE_SOURCE) opts.push_back("-DTDA_LOGLIKE_SOURCE");
   if (mala) opts.push_back("-DTDA_USER_MALA");
+  if (prior_source) opts.push_back("-DTDA_PRIOR_SOURCE");  // (never together with MALA: tda_engine_init refuses that)
   if (hiprtcCompileProgram(prog, (int)opts.size(), opts.data()) != HIPRTC_SUCCESS) {
     size_t n = 0;
     (void)hiprtcGetProgramLogSize(prog, &n);
@@ -58,6 +59,8 @@ int compile_user_program(const char* source, int noise_kind, bool mala, UserProg
                                    "double y, double p, int o)");
     if (!mala && log.find("tda_loglike_term_missing") != std::string::npos)
       return fail(TDA_ERR_INVALID, "a source-defined likelihood: the source defines no __device__ double tda_loglike_term(double f, double y, double p, int o)");
+    if (log.find("tda_logprior_term_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines no __device__ double tda_logprior_term(double x, double p, double q, int j)");
     if (log.size() > 400) log.resize(400);
     return fail(TDA_ERR_INVALID, "the forward-model source does not compile%s: %s", mala ? " with the MALA kernels" : "", log.c_str());
   }

@@ -125,7 +125,8 @@ class Engine:
             self._ck(self.lib.tda_engine_set_proposal_spectrum(self.h, _ptr(V), _ptr(lam)))
 
     def set_prior_joint(self, kinds, loc, scale):
-        """JointPrior of scalar components: kinds[j] 0 = norm(loc, scale), 1 = uniform(loc, scale)"""
+        """JointPrior of scalar components: kinds[j] 0 = norm(loc, scale), 1 = uniform(loc, scale); or 2 (_lib.PRIOR_SOURCE) for
+        every j: the levels' HIP sources define `tda_logprior_term(x, p, q, j)`, loc / scale are its p / q"""
         kinds = np.ascontiguousarray(np.asarray(kinds, dtype=np.int32))
         loc, scale = _f64(loc), _f64(scale)
         assert kinds.shape == loc.shape == scale.shape == (self.dim,)

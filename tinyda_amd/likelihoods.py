@@ -3,8 +3,11 @@
 All are *unnormalised* (-1/2 r^T Sigma^-1 r).  `GaussianLogLike` is the reference's factory: a diagonal
 covariance with equal entries becomes isotropic, a diagonal one diagonal, anything else dense
 (distributions.py:237-243).  Each class also reports how the device engine should see it (`_lowering`).
-`DeviceLogLike` (extension) is a separable log-likelihood given as HIP source, for everything that is not Gaussian.
+`DeviceLogLike` (extension) is a separable log-likelihood given as HIP source, for everything that is not Gaussian;
+`DevicePrior` (extension) the same for a prior of independent components, and `JointPrior` lowers lists of scipy families
+through it with the term library `csrc/tda_prior_families.h`.
 """
+import os
 import re
 
 import numpy as np
@@ -159,6 +162,144 @@ class DeviceLogLike:
         return _lib.NOISE_SOURCE, self.parameters
 
 
+class DevicePrior:
+    """A prior of independent components given as HIP source (extension; the reference's JointPrior takes any
+    scipy.stats.rv_continuous per parameter and evaluates it in Python, distributions.py:8-56):
+    log p(theta) = sum_j term(theta_j, p_j, q_j, j).  The source must define
+
+        __device__ double tda_logprior_term(double x, double p, double q, int j);       // term of parameter j
+
+    `p` and `q` hold one value per parameter (a location and a scale, say; zeros / ones when not given) and are passed on as
+    given; constants shared by all parameters are literals in the source.  The function is pure.  A term that is NaN or -inf
+    (outside the support) rejects the proposal.  Priors that couple parameters are not covered.  It is compiled into the
+    programs of the levels' `DeviceModel`s, so it lowers beside such models only (all levels of a hierarchy share it).
+
+    `reference`, if given, is any object with `logpdf(theta)` (and optionally `rvs` / `ppf`) -- a `JointPrior`, say -- and
+    serves the host protocol; `sample()` draws missing initial parameters through its `ppf`, or else from its
+    `rvs(random_state=generator)`."""
+
+    def __init__(self, source, dim, p=None, q=None, reference=None):
+        self.source = str(source)
+        self.dim = int(dim)
+        if self.dim < 1:
+            raise ValueError("dim must be >= 1")
+        self.p = np.zeros(self.dim) if p is None else np.atleast_1d(np.asarray(p, dtype=np.float64))
+        self.q = np.ones(self.dim) if q is None else np.atleast_1d(np.asarray(q, dtype=np.float64))
+        if self.p.shape != (self.dim,) or self.q.shape != (self.dim,):
+            raise ValueError("p and q must be vectors with one entry per parameter")
+        if not (np.all(np.isfinite(self.p)) and np.all(np.isfinite(self.q))):
+            raise ValueError("p and q must be finite")
+        if not re.search(r"\btda_logprior_term\s*\(", _strip_comments(self.source)):
+            raise ValueError("the source must define __device__ double tda_logprior_term(double x, double p, double q, int j)")
+        self.reference = reference
+
+    def _host(self, name):
+        fn = getattr(self.reference, name, None)
+        if fn is None:
+            raise TypeError("this DevicePrior has no host reference implementation of %s; run it with backend='hip'%s"
+                            % (name, " and initial_parameters" if name == "rvs" else ""))
+        return fn
+
+    def logpdf(self, x):
+        return self._host("logpdf")(x)
+
+    def rvs(self, *args, **kwargs):
+        return self._host("rvs")(*args, **kwargs)
+
+    def ppf(self, x):
+        return self._host("ppf")(x)
+
+    def _source_lowering(self):
+        """(kinds, p, q, source) with every kind = PRIOR_SOURCE: what Posterior._lowering hands to the engine"""
+        return np.full(self.dim, _lib.PRIOR_SOURCE, dtype=np.int32), self.p, self.q, self.source
+
+
+# the scipy.stats families of csrc/tda_prior_families.h, in the order of its ids, with the number of shape parameters
+_FAMILIES = (("norm", 0), ("uniform", 0), ("lognorm", 1), ("gamma", 1), ("invgamma", 1), ("beta", 2), ("expon", 0), ("halfnorm", 0),
+             ("laplace", 0), ("cauchy", 0), ("t", 1), ("truncnorm", 2), ("weibull_min", 1))
+_FAMILY_ID = {name: i for i, (name, _) in enumerate(_FAMILIES)}
+
+
+def _log_gauss_mass(a, b):
+    """log(Phi(b) - Phi(a)) without cancellation in either tail"""
+    from scipy.special import log_ndtr
+
+    if a > 0.0:
+        a, b = -b, -a
+    hi, lo = log_ndtr(b), log_ndtr(a)
+    return float(hi + np.log1p(-np.exp(lo - hi)))
+
+
+def _family_constant(name, shapes):
+    """the part of the family's log-density at z that does not depend on z (the term library adds it, minus log(scale))"""
+    from scipy.special import betaln, gammaln
+
+    if name == "norm":
+        return -0.5 * np.log(2.0 * np.pi)
+    if name == "lognorm":
+        return -np.log(shapes[0]) - 0.5 * np.log(2.0 * np.pi)
+    if name in ("gamma", "invgamma"):
+        return -float(gammaln(shapes[0]))
+    if name == "beta":
+        return -float(betaln(shapes[0], shapes[1]))
+    if name == "halfnorm":
+        return 0.5 * np.log(2.0 / np.pi)
+    if name == "laplace":
+        return -np.log(2.0)
+    if name == "cauchy":
+        return -np.log(np.pi)
+    if name == "t":
+        nu = shapes[0]
+        return float(gammaln(0.5 * (nu + 1.0)) - gammaln(0.5 * nu)) - 0.5 * np.log(nu * np.pi)
+    if name == "truncnorm":
+        return -0.5 * np.log(2.0 * np.pi) - _log_gauss_mass(shapes[0], shapes[1])
+    if name == "weibull_min":
+        return np.log(shapes[0])
+    return 0.0  # uniform, expon
+
+
+def _family_component(dist):
+    """(family id, a, b, c, loc, scale) of a frozen scipy.stats distribution of one of _FAMILIES, else None"""
+    import scipy.stats as st
+
+    gen = getattr(dist, "dist", None)
+    name = getattr(gen, "name", None)
+    if not isinstance(gen, st.rv_continuous) or name not in _FAMILY_ID or getattr(st, name, None).__class__ is not gen.__class__:
+        return None
+    try:  # (_parse_args and _argcheck are scipy's own helpers: where a release lacks them the component stays host-only)
+        shapes, loc, scale = gen._parse_args(*dist.args, **dist.kwds)
+        shapes = tuple(float(s) for s in shapes)
+        loc, scale = float(loc), float(scale)
+        valid = len(shapes) == _FAMILIES[_FAMILY_ID[name]][1] and bool(np.all(gen._argcheck(*shapes)))
+    except (AttributeError, TypeError, ValueError):
+        return None
+    if not (valid and np.all(np.isfinite(shapes + (loc, scale))) and scale > 0.0):
+        return None
+    c = float(_family_constant(name, shapes)) - np.log(scale)
+    if not np.isfinite(c):
+        return None
+    return (_FAMILY_ID[name],) + (shapes + (0.0, 0.0))[:2] + (c, loc, scale)
+
+
+def _family_prologue(rows):
+    """the tables that csrc/tda_prior_families.h reads, one row (family id, a, b, c) per parameter; the numbers are written as
+    exact literals (repr round-trips a double)"""
+    n = len(rows)
+
+    def table(ctype, name, col, fmt):
+        return "static __device__ const %s %s[%d] = {%s};\n" % (ctype, name, n, ", ".join(fmt(r[col]) for r in rows))
+
+    return ("#define TDA_PRIOR_DIM %d\n" % n + table("int", "tda_prior_family", 0, lambda v: "%d" % v)
+            + table("double", "tda_prior_a", 1, lambda v: repr(float(v))) + table("double", "tda_prior_b", 2, lambda v: repr(float(v)))
+            + table("double", "tda_prior_c", 3, lambda v: repr(float(v))))
+
+
+def family_library_source():
+    """the text of the term library shipped with the package (csrc/tda_prior_families.h)"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "tda_prior_families.h")) as fh:
+        return fh.read()
+
+
 class JointPrior:
     """A list of independent scalar priors, one per parameter, in parameter order (tinyDA/distributions.py:8-100)."""
 
@@ -183,7 +324,8 @@ class JointPrior:
         return np.column_stack([dist.ppf(col) for dist, col in zip(self.distributions, np.asarray(x).T)])
 
     def _lowering(self):
-        """(kinds, loc, scale) when every component is a frozen scipy norm or uniform, else None."""
+        """(kinds, loc, scale) when every component is a frozen scipy norm or uniform, else None (then _source_lowering may
+        still lower the list)."""
         kinds, loc, scale = [], [], []
         for dist in self.distributions:
             name = getattr(getattr(dist, "dist", None), "name", None)
@@ -194,3 +336,14 @@ class JointPrior:
             loc.append(float(l))
             scale.append(float(s))
         return np.array(kinds, dtype=np.int32), np.array(loc), np.array(scale)
+
+    def _source_lowering(self):
+        """(kinds, loc, scale, source) with every kind = PRIOR_SOURCE when all components are frozen scipy distributions of the
+        families of csrc/tda_prior_families.h -- the source is that library behind a prologue with the components' tables --
+        else None (a non-frozen object, an unlisted or discrete family: host protocol).  Posterior._lowering asks for it when
+        _lowering() has declined, so lists of norm / uniform alone never come here."""
+        rows = [_family_component(dist) for dist in self.distributions]
+        if not rows or any(r is None for r in rows):
+            return None
+        return (np.full(len(rows), _lib.PRIOR_SOURCE, dtype=np.int32), np.array([r[4] for r in rows]), np.array([r[5] for r in rows]),
+                _family_prologue(rows) + family_library_source())

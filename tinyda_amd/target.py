@@ -2,6 +2,7 @@
 import numpy as np
 
 from . import _lib
+from .likelihoods import DevicePrior
 from .records import Link
 from .models import BatchedModel, DeviceModel, LinearModel, Rosenbrock
 
@@ -44,10 +45,24 @@ class Posterior:
         (opaque Python model, non-Gaussian prior, ...)."""
         prior = self.prior
         joint = None
-        if hasattr(prior, "distributions") and hasattr(prior, "_lowering"):  # JointPrior of scalar norm / uniform components
-            joint = prior._lowering()
+        if isinstance(prior, DevicePrior) or (hasattr(prior, "distributions") and hasattr(prior, "_lowering")):
+            # JointPrior of scalar components, DevicePrior
+            joint = None if isinstance(prior, DevicePrior) else prior._lowering()
             if joint is None:
-                return None
+                # source-defined prior (DevicePrior, or a JointPrior of scipy families through the term library): its function is
+                # compiled with the model (+ likelihood), one program per level; the moments are placeholders nothing reads
+                joint = getattr(prior, "_source_lowering", lambda: None)()
+                if joint is None:
+                    return None
+                kinds, p, q, src = joint
+                low = self._lowering_with(np.zeros(kinds.shape[0]), np.eye(kinds.shape[0]))
+                if low is not None:
+                    low["prior_joint"] = (kinds, p, q)
+                    low["prior_source"] = dict(source=src, p=p, q=q, label="DevicePrior" if isinstance(prior, DevicePrior)
+                                               else "JointPrior of scipy families (source-defined prior)")
+                    if "source" in low:
+                        low["source"] = low["source"] + "\n" + src
+                return low
             kinds, loc, scale = joint
             low = self._lowering_with(np.where(kinds == 0, loc, loc + 0.5 * scale),
                                       np.diag(np.where(kinds == 0, scale ** 2, scale ** 2 / 12.0)))
