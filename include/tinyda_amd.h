@@ -416,7 +416,19 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
  * tda_gradient (the sensitivity is then d term / d f).  A source without tda_loglike_term (MALA: without
  * tda_loglike_term_grad, at tda_engine_init) returns TDA_ERR_INVALID naming the signature.  tda_engine_init refuses it with
  * TDA_ERR_UNSUPPORTED under DREAM(Z), Independence, operator-weighted pCN, an error model and randomised subchain lengths;
- * tda_engine_set_level / _callback refuse the kind.  Likelihoods that couple outputs are not covered. */
+ * tda_engine_set_level / _callback refuse the kind.  Likelihoods that couple outputs are not covered.
+ * Wave-cooperative models (one solve gives all outputs: an integrator, a time-stepping scheme, a tridiagonal solve): instead of
+ * tda_forward the source may define (the engine looks for the identifiers in the comment-stripped source; with both, this one is used)
+ *     #define TDA_WORKSPACE 3072   // optional: doubles of LDS scratch of the chain's own, handed over as `work` (default 0: null)
+ *     __device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane);
+ * called once per evaluation by all 64 lanes of the chain's wave, converged (also lanes >= dim).  theta: LDS, read-only, dim
+ * entries; out: LDS, n_outputs doubles, NaN before the call -- an entry left unwritten rejects the proposal like any NaN output.
+ * __syncthreads() inside is legal and a wave barrier (one wave per workgroup).  It serves every place tda_forward does.  MALA:
+ * tda_gradient may likewise be
+ *     __device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane);
+ * grad: LDS, 128 doubles, zero before the call, grad[j] = (J^T sensitivity)_j for j < dim; `work` holds what tda_forward_wave left
+ * at the same theta.  Either form of the model goes with either form of the gradient.  LDS per chain = 8 (m + 128 +
+ * TDA_WORKSPACE) bytes (+ 1 KiB with tda_gradient_wave), at most 64 KiB: more returns TDA_ERR_UNSUPPORTED with the byte counts. */
 int tda_engine_set_level_source(tda_engine* e, int level, const char* source, int32_t m, const double* data,
                                 int32_t noise_kind, const double* noise);
 

@@ -301,6 +301,7 @@ struct Level {
   UserProgram uprog;       // tda_user_steps / tda_user_eval / tda_user_level_action
   bool uprog_prior = false;  // uprog was compiled with -DTDA_PRIOR_SOURCE (ensure_user_programs rebuilds it when the prior changed since)
   std::string usrc;        // the model source (the MALA program is compiled from it at init)
+  bool fwd_wave = false, grad_wave = false;  // usrc defines tda_forward_wave / tda_gradient_wave (comments do not count)
   UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0
   DevBuf<double> udata, uw;
   DevBuf<double> upar;  // TDA_NOISE_SOURCE: the per-output parameters of the source's tda_loglike_term (as given, not inverted)
@@ -1075,7 +1076,7 @@ int ext_level_dense(tda_engine* /*e*/, Level& lv, int m, const double* cov) {
 // F[N][m] <- model(prop[N][d]) of a level whose model lives outside the engine's kernels: a batched host callback (through
 // page-locked staging buffers, one synchronisation) or a source-defined model (tda_user_eval, stays on the stream)
 int ext_model_outputs(tda_engine* e, const Level& lv) {
-  if (lv.model == MODEL_USER) return launch_user_eval(lv.uprog.eval, e->N, e->d, lv.m, lv.cb_prop.p, lv.cb_F.p, e->stream);
+  if (lv.model == MODEL_USER) return launch_user_eval(lv.uprog.eval, e->N, e->d, lv.m, lv.cb_prop.p, lv.cb_F.p, lv.uprog.out_lds, e->stream);
   if (lv.model == MODEL_LINEAR) {
     if (lv.Apk.p) {  // on the matrix cores, every operator fragment serving a 16-chain tile
       DISPATCH_DPAD_W(e->DP, hipLaunchKernelGGL((k_linear_outputs<DPAD>), dim3((unsigned)(e->NP / 16)), dim3(256), 0, e->stream, (long long)e->N,
@@ -1118,7 +1119,7 @@ int ensure_user_programs(tda_engine* e) {
   for (Level& lv : e->levels) {
     if (!lv.set || lv.model != MODEL_USER || lv.uprog_prior == e->prior_source) continue;
     lv.uprog.unload();
-    if (int rc = compile_user_program(lv.usrc.c_str(), lv.noise_kind, false, e->prior_source, &lv.uprog)) return rc;
+    if (int rc = compile_user_program(lv.usrc.c_str(), lv.noise_kind, false, e->prior_source, lv.fwd_wave, false, lv.m, &lv.uprog)) return rc;
     lv.uprog_prior = e->prior_source;
   }
   return TDA_OK;
@@ -1147,7 +1148,7 @@ int launch_eval(tda_engine* e, int level, double* theta, double* lp, double* ll)
     ua.lp = lp;
     ua.ll = ll;
     ua.scaling = e->scaling.p;
-    return launch_user(e->levels[level].uprog.steps, ua, 0, e->stream);
+    return launch_user(e->levels[level].uprog.steps, ua, e->levels[level].uprog.out_lds, e->stream);
   }
   StepArgs a{};
   fill_level(e, e->levels[level], a);

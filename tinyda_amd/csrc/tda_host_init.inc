@@ -265,7 +265,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;
   if (user_mala && !e->levels[0].uprog_mala.mod) {  // the second program: GRW / pCN / AM engines never build it
     Level& l0 = e->levels[0];
-    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, false, &l0.uprog_mala))) return rc;
+    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, false, l0.fwd_wave, l0.grad_wave, l0.m, &l0.uprog_mala))) return rc;
   }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;

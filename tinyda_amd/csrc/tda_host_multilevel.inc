@@ -82,7 +82,7 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
       ua.ring = adaptive ? e->ml_ring.p : nullptr;
       ua.ring_P = e->ring_P;
       ua.ring_pos = rp;
-      if ((urc = launch_user(e->levels[0].uprog.steps, ua, 0, e->stream))) return urc;
+      if ((urc = launch_user(e->levels[0].uprog.steps, ua, e->levels[0].uprog.out_lds, e->stream))) return urc;
       rp += n;
       s += n;
       cc[0] += (int)n;
@@ -294,7 +294,7 @@ static int run_ext_hierarchy_block(tda_engine* e, const MLArgs& ma, int64_t S, b
         ua.ring_P = e->ring_P;
         ua.ring_pos = rp++;
         ua.ysnap = (e->randomize && k == 0) ? e->ml_ysnap.p : nullptr;
-        int lrc = launch_user(lq.uprog.level, ua, 0, e->stream);
+        int lrc = launch_user(lq.uprog.level, ua, lq.uprog.out_lds, e->stream);
         if (lrc) return lrc;
         cc[k] = 0;
         cc[q] += 1;

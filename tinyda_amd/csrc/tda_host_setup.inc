@@ -324,7 +324,9 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
   Level& lv = e->levels[level];
   lv.uprog.unload();
   lv.uprog_mala.unload();
-  int rc = compile_user_program(source, noise_kind, false, e->prior_source, &lv.uprog);
+  lv.fwd_wave = source_defines(source, "tda_forward_wave");  // the wave forms: one call per evaluation by the chain's whole wave
+  lv.grad_wave = source_defines(source, "tda_gradient_wave");
+  int rc = compile_user_program(source, noise_kind, false, e->prior_source, lv.fwd_wave, false, m, &lv.uprog);
   if (rc) return rc;
   lv.uprog_prior = e->prior_source;  // (a prior set later: tda_engine_init compiles again, ensure_user_programs)
   lv.usrc = source;

@@ -384,7 +384,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       ua.rec_stats = sa.rec_stats;
       ua.rec_acc = sa.rec_acc;
       ScopedTimer tm(e, 1);
-      if ((urc = launch_user(lv.uprog.steps, ua, 0, e->stream))) return urc;
+      if ((urc = launch_user(lv.uprog.steps, ua, lv.uprog.out_lds, e->stream))) return urc;
     } else {
       ScopedTimer tm(e, 1);
       DISPATCH_DPAD_W(e->DP, launch_steps<DPAD>(sa, NP / 16, lds, e->stream));

@@ -5,7 +5,13 @@
 // callable per chain and step, posterior.py:95-96).  One wave per chain: lane j owns parameter j (and j + 64 at 65 .. 128
 // parameters), the lanes stride over the outputs.  Same step semantics, records and RNG inputs as k_mh_steps; proposals,
 // adaptation and Cholesky stay the engine's own kernels.
-// Three compile options select what is built (the file itself never defines them):
+// A model whose outputs all come from one solve (an integrator, a time-stepping scheme, a tridiagonal solve) defines the
+// wave-cooperative form instead: the 64 lanes of the chain's wave call it together, once per evaluation,
+//     __device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane);
+// theta and out are LDS (out: n_outputs doubles, NaN before the call: an entry left unwritten rejects the proposal), `work` is
+// TDA_WORKSPACE doubles of LDS of the chain's own (a #define of the source; 0 / undefined: null), __syncthreads() inside is legal
+// and a wave barrier (one wave per workgroup).
+// Five compile options select what is built (the file itself never defines them):
 //   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
 //                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
 //     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
@@ -16,6 +22,11 @@
 //   -DTDA_PRIOR_SOURCE    source-defined prior (tda_engine_set_prior_joint, kind TDA_PRIOR_SOURCE): log p(theta) = sum_j
 //                         tda_logprior_term(theta_j, p_j, q_j, j), defined by the source; the args' `pr_mean` / `pr_pinv` then carry
 //                         p / q as given.  tda_user_steps alone evaluates a prior; the MALA program does not take the switch.
+//   -DTDA_FORWARD_WAVE    the source defines tda_forward_wave: the outputs are taken from LDS (s_out[m], dynamic; the MALA program
+//                         lets the model write into its s_sens[m]) after one call, not from tda_forward(theta, dim, o) per output
+//   -DTDA_GRADIENT_WAVE   (MALA program) the source defines the vector-Jacobian product in the same form, one call for all parameters,
+//     __device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane);
+//                         grad: LDS, 128 doubles, zero before the call; `work` is what tda_forward_wave left at the same theta
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -23,7 +34,16 @@ __device__ double tda_forward(const double* theta, int dim, int o);
 // Fallbacks a call resolves to when the source does not define a function of the contract's signature (a non-template function of
 // that signature wins overload resolution against them); the static_asserts below turn them into a message, not an unresolved
 // symbol at load.
-#ifdef TDA_USER_MALA
+#ifdef TDA_FORWARD_WAVE
+struct tda_forward_wave_missing {};
+template <class L>
+__device__ tda_forward_wave_missing tda_forward_wave(const double*, int, double*, int, double*, L) { return {}; }
+#endif
+#if defined(TDA_USER_MALA) && defined(TDA_GRADIENT_WAVE)
+struct tda_gradient_wave_missing {};
+template <class L>
+__device__ tda_gradient_wave_missing tda_gradient_wave(const double*, int, const double*, int, double*, double*, L) { return {}; }
+#elif defined(TDA_USER_MALA)
 struct tda_gradient_missing {};
 template <class J>
 __device__ tda_gradient_missing tda_gradient(const double*, int, const double*, int, J) { return {}; }
@@ -47,7 +67,14 @@ __device__ tda_logprior_term_missing tda_logprior_term(double, double, double, J
 
 #include "tda_user_source.h"
 
-#ifdef TDA_USER_MALA
+#ifdef TDA_FORWARD_WAVE
+static_assert(!__is_same(decltype(tda_forward_wave((const double*)nullptr, 0, (double*)nullptr, 0, (double*)nullptr, 0)), tda_forward_wave_missing),
+              "tda_forward_wave_missing: the wave form of the model is __device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)");
+#endif
+#if defined(TDA_USER_MALA) && defined(TDA_GRADIENT_WAVE)
+static_assert(!__is_same(decltype(tda_gradient_wave((const double*)nullptr, 0, (const double*)nullptr, 0, (double*)nullptr, (double*)nullptr, 0)), tda_gradient_wave_missing),
+              "tda_gradient_wave_missing: the wave form of the gradient is __device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane)");
+#elif defined(TDA_USER_MALA)
 static_assert(!__is_same(decltype(tda_gradient((const double*)nullptr, 0, (const double*)nullptr, 0, 0)), tda_gradient_missing),
               "tda_gradient_missing: MALA needs __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)");
 #endif
@@ -62,6 +89,27 @@ static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_
 #ifdef TDA_PRIOR_SOURCE
 static_assert(!__is_same(decltype(tda_logprior_term(0.0, 0.0, 0.0, 0)), tda_logprior_term_missing),
               "tda_logprior_term_missing: a source-defined prior needs __device__ double tda_logprior_term(double x, double p, double q, int j)");
+#endif
+
+// The wave forms' LDS: the outputs s_out[m] (dynamic, sized by the host) and the model's workspace.  A program without the
+// switches has neither: the names are null pointers that no code reads.
+#if (defined(TDA_FORWARD_WAVE) || defined(TDA_GRADIENT_WAVE)) && defined(TDA_WORKSPACE) && TDA_WORKSPACE > 0
+#define TDA_DECLARE_WORK __shared__ double s_work[TDA_WORKSPACE]
+#else
+#define TDA_DECLARE_WORK double* const s_work = nullptr
+#endif
+#ifdef TDA_FORWARD_WAVE
+#define TDA_DECLARE_OUT extern __shared__ double s_out[]
+// every output of the model at the parameters in s_th, by one converged call of the wave; the barriers order the NaN fill, the
+// model's writes (any lane may write any entry) and the readers.  The callers' own barriers keep earlier readers of `out` away.
+__device__ __forceinline__ void tda_outputs_wave(const double* s_th, int lane, int d, int m, double* out, double* s_work) {
+  for (int o = lane; o < m; o += 64) out[o] = __builtin_nan("");
+  __syncthreads();
+  tda_forward_wave(s_th, d, out, m, s_work, lane);
+  __syncthreads();
+}
+#else
+#define TDA_DECLARE_OUT double* const s_out = nullptr
 #endif
 
 __device__ __forceinline__ double tda_wave_sum(double v) {
@@ -82,13 +130,24 @@ __device__ __forceinline__ double tda_loglike_of_sum(double sum, const double* w
 #ifndef TDA_USER_MALA
 // log-likelihood of the model outputs at the parameters in s_th, for the whole wave (link.py:48 takes any loglike).  The level's
 // fields come in one by one: with the argument struct passed whole the kernels no longer compile to the instructions they had.
-__device__ __forceinline__ double tda_loglike(const double* s_th, int lane, int d, int m, const double* data, const double* w, double var) {
+#ifdef TDA_FORWARD_WAVE
+#define TDA_OUTPUT(o) s_out[o]
+#else
+#define TDA_OUTPUT(o) tda_forward(s_th, d, o)
+#endif
+__device__ __forceinline__ double tda_loglike(const double* s_th, int lane, int d, int m, const double* data, const double* w, double var, double* s_out,
+                                              double* s_work) {
   double sum = 0.0;
+#ifdef TDA_FORWARD_WAVE
+  tda_outputs_wave(s_th, lane, d, m, s_out, s_work);
+#else
+  (void)s_out, (void)s_work;
+#endif
 #ifdef TDA_LOGLIKE_SOURCE
-  for (int o = lane; o < m; o += 64) sum += tda_loglike_term(tda_forward(s_th, d, o), data[o], w[o], o);
+  for (int o = lane; o < m; o += 64) sum += tda_loglike_term(TDA_OUTPUT(o), data[o], w[o], o);
 #else
   for (int o = lane; o < m; o += 64) {
-    const double r = tda_forward(s_th, d, o) - data[o];
+    const double r = TDA_OUTPUT(o) - data[o];
     double sq = r * r;
     if (w) sq *= w[o];
     sum += sq;
@@ -98,6 +157,8 @@ __device__ __forceinline__ double tda_loglike(const double* s_th, int lane, int 
 }
 extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepArgs a) {
   __shared__ double s_th[128];  // (65 .. 128 parameters: a lane holds parameters `lane` and `lane + 64`)
+  TDA_DECLARE_OUT;
+  TDA_DECLARE_WORK;
   const int lane = threadIdx.x, lane2 = lane + 64;
   const long long c = blockIdx.x;
   if (c >= a.N) return;
@@ -123,7 +184,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
     s_th[lane] = prp;
     s_th[lane2] = prp2;
     __syncthreads();
-    const double ll_n = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var);
+    const double ll_n = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var, s_out, s_work);
 #ifdef TDA_PRIOR_SOURCE
     // source-defined prior: the sum of the components' terms (pm / pinv hold p / q); a component outside its support is -inf
     double pj = lj ? tda_logprior_term(prp, pm, pinv, lane) : 0.0;
@@ -184,6 +245,8 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
 // same decision, alignment and records as the engine's k_ext_level_action, with the model evaluated in place
 extern "C" __global__ void __launch_bounds__(64) tda_user_level_action(const UserLevelArgs a) {
   __shared__ double s_th[128];  // (65 .. 128 parameters: a second parameter per lane)
+  TDA_DECLARE_OUT;
+  TDA_DECLARE_WORK;
   const int lane = threadIdx.x, lane2 = lane + 64;
   const long long c = blockIdx.x;
   if (c >= a.N) return;
@@ -197,7 +260,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_level_action(const Use
   s_th[lane] = yj;
   s_th[lane2] = yj2;
   __syncthreads();
-  const double lln = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var);
+  const double lln = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var, s_out, s_work);
   const double y_lp = ys ? ys[a.DP] : a.lp[(size_t)k * a.NP + c], y_ll = ys ? ys[a.DP + 1] : a.ll[(size_t)k * a.NP + c];
   const double x_lp = a.lp[(size_t)q * a.NP + c], x_ll = a.ll[(size_t)q * a.NP + c];
   const int pkq = q * (q - 1) / 2 + k;
@@ -260,25 +323,41 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int 
   s_th[lane] = lane < d ? prop[c * d + lane] : 0.0;
   s_th[lane + 64] = lane + 64 < d ? prop[c * d + lane + 64] : 0.0;
   __syncthreads();
-  for (int o = lane; o < m; o += 64) F[c * m + o] = tda_forward(s_th, d, o);
+#ifdef TDA_FORWARD_WAVE
+  TDA_DECLARE_OUT;
+  TDA_DECLARE_WORK;
+  tda_outputs_wave(s_th, lane, d, m, s_out, s_work);
+#endif
+  for (int o = lane; o < m; o += 64) F[c * m + o] = TDA_OUTPUT(o);
 }
 
 #else  // TDA_USER_MALA
 // outputs of the model at the parameters in s_th: returns this lane's share of the sum that tda_loglike_of_sum finishes (the
 // weighted squares, or the terms of a source-defined likelihood) and leaves the sensitivity in s_sens: grad_loglike =
 // Sigma^-1 (y - F) (distributions.py:300-301 iso: 1 / var * r, :314-315 diag: w * r), or d term / d f
-__device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, int lane) {
+// (wave form: the model writes its outputs into s_sens, each lane then turns its own entries into sensitivities in place)
+#ifdef TDA_FORWARD_WAVE
+#define TDA_MALA_OUTPUT(o) s_sens[o]
+#else
+#define TDA_MALA_OUTPUT(o) tda_forward(s_th, a.d, o)
+#endif
+__device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, double* s_work, int lane) {
   double sum = 0.0;
+#ifdef TDA_FORWARD_WAVE
+  tda_outputs_wave(s_th, lane, a.d, a.m, s_sens, s_work);
+#else
+  (void)s_work;
+#endif
 #ifdef TDA_LOGLIKE_SOURCE
   for (int o = lane; o < a.m; o += 64) {
-    const double f = tda_forward(s_th, a.d, o);
+    const double f = TDA_MALA_OUTPUT(o);
     sum += tda_loglike_term(f, a.data[o], a.w[o], o);
     s_sens[o] = tda_loglike_term_grad(f, a.data[o], a.w[o], o);
   }
 #else
   const double iv = 1.0 / a.var;
   for (int o = lane; o < a.m; o += 64) {
-    const double f = tda_forward(s_th, a.d, o);
+    const double f = TDA_MALA_OUTPUT(o);
     const double r = f - a.data[o];
     double sq = r * r;
     if (a.w) sq *= a.w[o];
@@ -291,6 +370,10 @@ __device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const 
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
   extern __shared__ double s_sens[];  // [m]
   __shared__ double s_th[128];
+  TDA_DECLARE_WORK;
+#ifdef TDA_GRADIENT_WAVE
+  __shared__ double s_grad[128];  // J^T sens of the proposal, all parameters from one tda_gradient_wave call
+#endif
   const int lane = threadIdx.x, lane2 = lane + 64;
   const long long c = blockIdx.x;
   if (c >= a.N) return;
@@ -311,7 +394,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
     s_th[lane] = prp;
     s_th[lane2] = prp2;
     __syncthreads();
-    const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, lane));
+    const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, s_work, lane));
     double pj = 0.0;
     if (lj) {
       const double dv = prp - pm;
@@ -325,10 +408,21 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
     const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);
     const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
     const double post_n = lp_n + ll_n;               // link.py:48
+#ifdef TDA_GRADIENT_WAVE
+    s_grad[lane] = 0.0;  // (its readers of the previous step are behind the barriers above)
+    s_grad[lane2] = 0.0;
+#endif
     __syncthreads();  // s_sens complete
     // gradient at the proposal: grad log prior + J^T grad loglike (proposal.py:996-998; utils.py:273-287)
+#ifdef TDA_GRADIENT_WAVE
+    tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
+    __syncthreads();
+    const double gp = lj ? pinv * (pm - prp) + s_grad[lane] : 0.0;
+    const double gp2 = lj2 ? pinv2 * (pm2 - prp2) + s_grad[lane2] : 0.0;
+#else
     const double gp = lj ? pinv * (pm - prp) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
     const double gp2 = lj2 ? pinv2 * (pm2 - prp2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+#endif
     // transition densities (proposal.py:1000-1005): q(x|y) = -|x - y - s^2/2 grad(y)|^2 / (2 s^2)
     const double da = (cur - prp) - h * gp, da2 = (cur2 - prp2) - h * gp2;
     const double db = (prp - cur) - h * gc, db2 = (prp2 - cur2) - h * gc2;
@@ -375,6 +469,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserMalaArgs a) {
   extern __shared__ double s_sens[];
   __shared__ double s_th[128];
+  TDA_DECLARE_WORK;
   const int lane = threadIdx.x, lane2 = lane + 64;
   const long long c = blockIdx.x;
   if (c >= a.N) return;
@@ -384,9 +479,20 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserM
   s_th[lane] = th;
   s_th[lane2] = th2;
   __syncthreads();
-  (void)tda_mala_outputs(a, s_th, s_sens, lane);
+  (void)tda_mala_outputs(a, s_th, s_sens, s_work, lane);
+#ifdef TDA_GRADIENT_WAVE
+  __shared__ double s_grad[128];
+  s_grad[lane] = 0.0;
+  s_grad[lane2] = 0.0;
+  __syncthreads();
+  tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
+  __syncthreads();
+  if (lane < a.DP) a.grad[row + lane] = lj ? a.pr_pinv[lane] * (a.pr_mean[lane] - th) + s_grad[lane] : 0.0;
+  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? a.pr_pinv[lane2] * (a.pr_mean[lane2] - th2) + s_grad[lane2] : 0.0;
+#else
   __syncthreads();
   if (lane < a.DP) a.grad[row + lane] = lj ? a.pr_pinv[lane] * (a.pr_mean[lane] - th) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
   if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? a.pr_pinv[lane2] * (a.pr_mean[lane2] - th2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+#endif
 }
 #endif  // TDA_USER_MALA

@@ -47,13 +47,27 @@ class DeviceModel:
 
         __device__ double tda_forward(const double* theta, int dim, int o);   // output o of F(theta), 0 <= o < n_outputs
 
+    or, for a model whose outputs all come from one solve (an integrator, a time-stepping scheme, a tridiagonal solve), the
+    wave-cooperative form, which the 64 lanes of the chain's wave call together, once per evaluation (used when both are there):
+
+        #define TDA_WORKSPACE 3072   // optional: doubles of LDS scratch of the chain's own, handed over as `work` (default: none, null)
+        __device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane);
+        // theta, out: LDS; out is NaN before the call and an entry left unwritten rejects the proposal; __syncthreads() inside
+        // is legal and a wave barrier.  LDS per chain = 8 (n_outputs + 128 + TDA_WORKSPACE) bytes, at most 64 KiB.
+
     and may define the model's vector-Jacobian product, which MALA runs on (the device counterpart of the reference's
     `model.gradient(parameters, sensitivity)`, proposal.py:996-998):
 
         __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
         // (J(theta)^T sensitivity)_j, 0 <= j < dim
 
-    `has_gradient` says whether the source defines it (comments do not count).
+    or that in the wave form, one call for all parameters (grad: LDS, 128 doubles, zero before the call; `work` is what
+    tda_forward_wave left at the same theta):
+
+        __device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane);
+
+    `has_forward_wave` / `has_gradient_wave` say whether the source defines the wave forms, `has_gradient` whether it defines
+    either gradient (comments do not count).
 
     `reference`, if given, is a Python callable theta -> outputs used when the model is called on the host (host
     protocol, tests); without it the model only runs on the device.  `reference_gradient(theta, sensitivity)`, if
@@ -64,9 +78,13 @@ class DeviceModel:
         self.source = str(source)
         self.n_outputs = int(n_outputs)
         self.reference = reference
-        if "tda_forward" not in self.source:
-            raise ValueError("the source must define __device__ double tda_forward(const double* theta, int dim, int o)")
-        self.has_gradient = "tda_gradient" in _strip_comments(self.source)
+        code = _code_only(self.source)
+        self.has_forward_wave = re.search(r"\btda_forward_wave\b", code) is not None
+        self.has_gradient_wave = re.search(r"\btda_gradient_wave\b", code) is not None
+        if not (self.has_forward_wave or re.search(r"\btda_forward\b", code)):
+            raise ValueError("the source must define __device__ double tda_forward(const double* theta, int dim, int o) or __device__ void "
+                             "tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)")
+        self.has_gradient = self.has_gradient_wave or re.search(r"\btda_gradient\b", code) is not None
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:
             self.gradient = self._reference_gradient  # (an attribute only then: MALA.setup_proposal looks for it)
@@ -79,6 +97,13 @@ class DeviceModel:
         if self.reference is None:
             raise TypeError("this DeviceModel has no host reference implementation; run it with backend='hip'")
         return np.atleast_1d(np.asarray(self.reference(np.asarray(parameters, dtype=np.float64)), dtype=np.float64))
+
+
+def _code_only(source):
+    """HIP source without its // and /* */ comments, string literals and character literals: what the engine searches for the
+    identifiers of the wave forms (source_defines in csrc/tda_usermodel.inc skips the same; the engine's answer is what is
+    compiled, the attributes of DeviceModel only report it)."""
+    return re.sub(r"""//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\])*"|'(?:\\.|[^'\\])*'""", " ", source, flags=re.S)
 
 
 def _strip_comments(source):

@@ -95,7 +95,7 @@ class Posterior:
             if data.shape != (self.model.n_outputs,):
                 return None
             low = dict(prior_mean=mean, prior_cov=cov, source=self.model.source, has_gradient=self.model.has_gradient, A=None, b=None,
-                       data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
+                       has_forward_wave=self.model.has_forward_wave, has_gradient_wave=self.model.has_gradient_wave, data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
             if kind == _lib.NOISE_SOURCE:  # DeviceLogLike: its functions are compiled with the model, one program
                 low.update(source=self.model.source + "\n" + self.likelihood.source, loglike_source=True,
                            loglike_has_gradient=self.likelihood.has_gradient)
