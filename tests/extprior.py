@@ -1,7 +1,10 @@
 """What the source-defined-prior tests share: the 13 scipy families that JointPrior lowers through the term library
 (tinyda_amd/csrc/tda_prior_families.h), cycled to any dimension; FamilyPrior, the same prior as an oracle level's prior
-(scipy's own logpdf summed in parameter order); and a hand-written DevicePrior source (independent lognormals, p = log of
+(scipy's own logpdf summed in parameter order); host_library, the shipped library compiled for the host; and a hand-written DevicePrior source (independent lognormals, p = log of
 the median, q = sigma of the logarithm) with its NumPy twin."""
+import ctypes
+import subprocess
+
 import numpy as np
 import scipy.stats as st
 
@@ -84,6 +87,32 @@ def starts_near_lower_edges(comps, n, rng, q0=0.15):
         if np.isfinite(hi):
             th[:, j] = hi - np.abs(hi - th[:, j])
     return truth, th
+
+
+def host_library(tmp_path, comps):
+    """the library exactly as shipped, behind the prologue generated for `comps`, compiled for the host: term(x, j)"""
+    from tinyda_amd import likelihoods as lk
+
+    rows = [lk._family_component(c) for c in comps]
+    assert all(r is not None for r in rows)
+    src = ("#include <cmath>\nusing std::log; using std::log1p; using std::exp; using std::fabs;\n#define __device__\n"
+           + lk._family_prologue(rows) + lk.family_library_source()
+           + "\nextern \"C\" void terms(const double* x, const double* p, const double* q, int j, int n, double* out) {\n"
+             "  for (int i = 0; i < n; ++i) out[i] = tda_logprior_term(x[i], p[j], q[j], j);\n}\n")
+    cpp, so = tmp_path / "lib.cpp", tmp_path / "lib.so"
+    cpp.write_text(src)
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-o", str(so), str(cpp)], check=True)
+    lib = ctypes.CDLL(str(so))
+    p, q = np.array([r[4] for r in rows]), np.array([r[5] for r in rows])
+
+    def term(x, j):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.empty_like(x)
+        dp = ctypes.POINTER(ctypes.c_double)
+        lib.terms(x.ctypes.data_as(dp), p.ctypes.data_as(dp), q.ctypes.data_as(dp), ctypes.c_int(j), ctypes.c_int(x.size), out.ctypes.data_as(dp))
+        return out
+
+    return term, rows
 
 
 # ---- a hand-written DevicePrior: independent lognormals, p = log median, q = sigma of log theta --------------------------------

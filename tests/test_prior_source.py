@@ -2,7 +2,6 @@
 library against scipy's logpdf, the host methods, the lowering rules, the host protocol and the oracle level against the
 reference's own chains (tests/golden/g19_prior_families_*.npz, gen_golden_prior_source.py), and the hiprtc program
 compiled offline for gfx950 with the prior switch."""
-import ctypes
 import os
 import re
 import subprocess
@@ -17,6 +16,7 @@ from oracle import tinyda_oracle as orc
 from . import extloglike as xl
 from . import extprior as xp
 from .extmodel import np_forward, source
+from .extprior import host_library as _host_library
 from .test_loglike_source import CSRC, HIPCC, PROGRAM, needs_hipcc
 
 G19 = ("g19_prior_families_grw", "g19_prior_families_am")
@@ -56,32 +56,6 @@ def _device_prior(d, reference=True):
 
 
 # ---- 1. the shipped term library against scipy ------------------------------------------------------------------------------
-def _host_library(tmp_path, comps):
-    """the library exactly as shipped, behind the prologue generated for `comps`, compiled for the host: term(x, j)"""
-    from tinyda_amd import likelihoods as lk
-
-    rows = [lk._family_component(c) for c in comps]
-    assert all(r is not None for r in rows)
-    src = ("#include <cmath>\nusing std::log; using std::log1p; using std::exp; using std::fabs;\n#define __device__\n"
-           + lk._family_prologue(rows) + lk.family_library_source()
-           + "\nextern \"C\" void terms(const double* x, const double* p, const double* q, int j, int n, double* out) {\n"
-             "  for (int i = 0; i < n; ++i) out[i] = tda_logprior_term(x[i], p[j], q[j], j);\n}\n")
-    cpp, so = tmp_path / "lib.cpp", tmp_path / "lib.so"
-    cpp.write_text(src)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-o", str(so), str(cpp)], check=True)
-    lib = ctypes.CDLL(str(so))
-    p, q = np.array([r[4] for r in rows]), np.array([r[5] for r in rows])
-
-    def term(x, j):
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        out = np.empty_like(x)
-        dp = ctypes.POINTER(ctypes.c_double)
-        lib.terms(x.ctypes.data_as(dp), p.ctypes.data_as(dp), q.ctypes.data_as(dp), ctypes.c_int(j), ctypes.c_int(x.size), out.ctypes.data_as(dp))
-        return out
-
-    return term, rows
-
-
 def test_term_library_against_scipy_logpdf(tmp_path):
     """Every family: 2000 draws from the component, 200 wide normal points (most of them outside a bounded support) and the
     support's edges.  The -inf sets must be identical.  Bound: the term is g(z) + c, and the library and scipy each reach it

@@ -221,13 +221,34 @@ _FAMILY_ID = {name: i for i, (name, _) in enumerate(_FAMILIES)}
 
 
 def _log_gauss_mass(a, b):
-    """log(Phi(b) - Phi(a)) without cancellation in either tail"""
-    from scipy.special import log_ndtr
+    """log(Phi(b) - Phi(a)) for a < b, to a few roundings of its own magnitude wherever the window lies and however narrow it is"""
+    from scipy.special import erf, log_ndtr
 
+    if a <= 0.0 <= b:  # the window holds 0: the two halves add, nothing cancels (log_ndtr of both bounds would sit near log 0.5)
+        return float(np.log(0.5 * (erf(b / np.sqrt(2.0)) - erf(a / np.sqrt(2.0)))))
     if a > 0.0:
         a, b = -b, -a
-    hi, lo = log_ndtr(b), log_ndtr(a)
-    return float(hi + np.log1p(-np.exp(lo - hi)))
+    # a < b < 0.  w = log(phi(b) / phi(a)) bounds log(Phi(b) / Phi(a)) from below (the hazard phi / Phi of a negative t is above |t|)
+    w = 0.5 * (b - a) * -(a + b)
+    if w < 0.5:
+        # a narrow window: the difference of the two tails cancels, so integrate phi(t) / phi(a) = exp(-s (a + s / 2)), t = a + s,
+        # over it (entire, rising from 1 to e^w < 1.65 over a width below 1: 16 Gauss-Legendre nodes leave nothing above rounding)
+        t, wt = np.polynomial.legendre.leggauss(16)
+        s = 0.5 * (b - a) * (t + 1.0)
+        return float(-0.5 * a * a - 0.5 * np.log(2.0 * np.pi) + np.log(0.5 * (b - a) * np.sum(wt * np.exp(-s * (a + 0.5 * s)))))
+    hi, lo = log_ndtr(b), log_ndtr(a)  # lo - hi <= -w: its rounding stays a rounding of the result
+    return float(hi + np.log(-np.expm1(lo - hi)))
+
+
+def _log_gamma_half_step(x):
+    """log(Gamma(x + 1/2) / Gamma(x)): the difference of two gammaln loses |gammaln(x)| eps, so from x = 100 on the asymptotic
+    series takes over (its first dropped term is below 2e-21 there)"""
+    from scipy.special import gammaln
+
+    if x < 100.0:
+        return float(gammaln(x + 0.5) - gammaln(x))
+    r = 1.0 / (x * x)
+    return 0.5 * np.log(x) - (1.0 / 8.0 - (1.0 / 192.0 - (1.0 / 640.0 - 17.0 / 14336.0 * r) * r) * r) / x
 
 
 def _family_constant(name, shapes):
@@ -250,7 +271,7 @@ def _family_constant(name, shapes):
         return -np.log(np.pi)
     if name == "t":
         nu = shapes[0]
-        return float(gammaln(0.5 * (nu + 1.0)) - gammaln(0.5 * nu)) - 0.5 * np.log(nu * np.pi)
+        return _log_gamma_half_step(0.5 * nu) - 0.5 * np.log(nu * np.pi)
     if name == "truncnorm":
         return -0.5 * np.log(2.0 * np.pi) - _log_gauss_mass(shapes[0], shapes[1])
     if name == "weibull_min":
