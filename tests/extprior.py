@@ -1,12 +1,20 @@
 """What the source-defined-prior tests share: the 13 scipy families that JointPrior lowers through the term library
 (tinyda_amd/csrc/tda_prior_families.h), cycled to any dimension; FamilyPrior, the same prior as an oracle level's prior
 (scipy's own logpdf summed in parameter order); host_library, the shipped library compiled for the host; and a hand-written DevicePrior source (independent lognormals, p = log of
-the median, q = sigma of the logarithm) with its NumPy twin."""
+the median, q = sigma of the logarithm) with its NumPy twin; and, for the GPU tests, the engine and the oracle level over
+extmodel's forward model under such a prior."""
 import ctypes
 import subprocess
 
 import numpy as np
 import scipy.stats as st
+
+from oracle import tinyda_oracle as orc
+
+from .extengine import PRIOR_SOURCE, set_proposal
+from .extmodel import np_forward
+
+SIGMA2 = 0.01  # the noise variance of the problems over extmodel's forward model
 
 FAMILY_NAMES = ("lognorm", "gamma", "beta", "norm", "uniform", "expon", "halfnorm", "invgamma", "laplace", "cauchy", "t",
                 "truncnorm", "weibull_min")
@@ -87,6 +95,40 @@ def starts_near_lower_edges(comps, n, rng, q0=0.15):
         if np.isfinite(hi):
             th[:, j] = hi - np.abs(hi - th[:, j])
     return truth, th
+
+
+def family_source(comps):
+    """(p, q, HIP source of the prior) exactly as sample() hands them over"""
+    import tinyda_amd as tda
+
+    _, p, q, src = tda.JointPrior(comps)._source_lowering()
+    return p, q, src
+
+
+def level_of(comps, m, y, shift=0.0, coup=0.5, noise=("iso", SIGMA2)):
+    return orc.CallableGaussianLevel(lambda th: np_forward(th, m, shift=shift, coup=coup), y, noise[0], noise[1], FamilyPrior(comps))
+
+
+def make_engine(comps, N, levels, prop, bs=0, seed=93, chain_offset=5, subchains=None):
+    """levels: [(model (+ likelihood) source, data, noise kind, noise)]; the prior is set first, so every level compiles once"""
+    from tinyda_amd.engine import Engine
+
+    p, q, psrc = family_source(comps)
+    e = Engine(N, len(comps), seed=seed, chain_offset=chain_offset, block_steps=bs, n_levels=len(levels))
+    e.set_prior_joint(np.full(len(comps), PRIOR_SOURCE), p, q)
+    for k, (src, y, kind, noise) in enumerate(levels):
+        e.set_level_source(k, src + "\n" + psrc, y, kind, noise)
+    set_proposal(e, prop)
+    if subchains is not None:
+        e.set_subchains(subchains, False)
+    return e
+
+
+def oracle_proposals_outside(ref, prior, z, prop):
+    """[N, T] True where the random-walk proposal of step t left a support (fixed scaling, C = I: theta + scaling z)"""
+    props = ref["theta"][:, :-1] + prop["scaling"] * z
+    N, T, d = props.shape
+    return ~prior.inside(props.reshape(-1, d)).reshape(N, T)
 
 
 def host_library(tmp_path, comps):

@@ -7,6 +7,8 @@ import scipy.stats as st
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import compare_levels, oracle_uniforms
+
 pytestmark = pytest.mark.gpu
 
 M = 70  # more outputs than lanes: the wave strides twice
@@ -153,7 +155,6 @@ def test_callback_hierarchy_matches_oracle(case):
     """Delayed Acceptance / MLDA with every level behind a batched host callback (host-sequenced level actions,
     k_ext_level_action) against the oracle's DAChain / MLDAChain restatement running the same NumPy models; engine on its
     own Philox stream, base-level normals exported, uniforms regenerated by the oracle's Philox."""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, N = 6, 19
@@ -197,7 +198,7 @@ def test_callback_hierarchy_matches_oracle(case):
     # one call per level for the initial links (level 0 twice: the single-level and the hierarchy initialisation), then one per local step
     for k in range(nl):
         assert all(c == (N, d) for c in calls[k]) and len(calls[k]) >= rows[k] + 1
-    us, _ = _oracle_uniforms(seed, N, rows, sl)
+    us, _ = oracle_uniforms(seed, N, rows, sl)
     prior = orc.MVNPrior(pm, np.diag(pv))
     levels = [orc.CallableGaussianLevel(models[k], y, "diag" if diag else "iso", noise, prior) for k in range(nl)]
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, None)
@@ -273,7 +274,6 @@ def test_multilevel_sampling_with_plain_python_models():
 def test_dense_noise_over_external_models(model_kind):
     """DefaultGaussianLogLike (correlated data noise) over a callback and over a source-defined model: single-level AM against
     the oracle, and as the fine level of a Delayed-Acceptance pair."""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tests.test_gpu_usermodel import SRC, np_model as src_model
     from tinyda_amd.engine import Engine
 
@@ -323,13 +323,10 @@ def test_dense_noise_over_external_models(model_kind):
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, _ = _oracle_uniforms(seed, N, rows, sl)
+    us, _ = oracle_uniforms(seed, N, rows, sl)
     levels = [orc.CallableGaussianLevel(model, y, "iso", 0.08 ** 2, prior), orc.CallableGaussianLevel(model, y, "dense", cov, prior)]
     res, _ = orc.run_multilevel(levels, dict(kind="pcn", scaling=0.04), sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, None)
-    for i in range(2):
-        sk = slice(1, None) if i == 1 else slice(None)
-        assert np.array_equal(outs[i][2], res[i]["accepted"][:, sk].T), "level %d accept masks differ" % i
-        np.testing.assert_allclose(outs[i][1][:, :, 2], res[i]["logpost"][:, sk].T, rtol=1e-10)
+    compare_levels(outs, res, states=False)
 
 
 @pytest.mark.parametrize("kind,model_kind", [("indep", "callback"), ("indep", "source"), ("owcn", "callback"), ("owcn", "source")])

@@ -17,16 +17,12 @@ from oracle import tinyda_oracle as orc
 from . import extloglike as xl
 from . import extprior as xp
 from . import extwave as xw
+from .extengine import (NOISE_SOURCE, PRIOR_SOURCE, assert_levels_resume_bitwise, assert_rate, assert_resume_bitwise, compare, compare_levels,
+                        compare_replay, oracle_uniforms, run_forward, run_levels_forward, set_proposal)
 
 pytestmark = pytest.mark.gpu
 
 SIGMA = 0.01
-PROP_KIND = {"grw": 0, "pcn": 1, "am": 2, "mala": 6}
-
-
-def set_proposal(e, prop):
-    kw = {k: v for k, v in prop.items() if k not in ("kind", "C", "C0")}
-    e.set_proposal(PROP_KIND[prop["kind"]], prop.get("C", prop.get("C0")), **kw)
 
 
 def make_engine(src, d, y, N, prop, bs=0, seed=93, chain_offset=5, sigma=SIGMA, prior=None):
@@ -43,32 +39,6 @@ def make_engine(src, d, y, N, prop, bs=0, seed=93, chain_offset=5, sigma=SIGMA, 
 def level_of(d, m, y, ksteps=48, sigma=SIGMA, prior=None, **kw):
     pm, pv = (np.zeros(d), np.ones(d)) if prior is None else prior
     return orc.CallableGaussianLevel(lambda th: xw.np_forward(th, m, ksteps, **kw), y, "iso", sigma ** 2, orc.MVNPrior(pm, np.diag(pv)))
-
-
-def assert_rate(accepted):
-    rate = accepted.mean()
-    print("oracle acceptance rate %.3f" % rate)
-    assert 0.1 <= rate <= 0.9, rate
-
-
-def compare(params, stats, acc, ref, span_form=False):
-    """masks exact, log-posterior 1e-10; states 1e-9 of themselves (atol 1e-12), as test_gpu_mala_source.py and, up to 64
-    parameters, test_gpu_prior_source.py hold them.  `span_form` (see span_form_applies): a state is held to 1e-9 of the larger
-    of itself and the largest magnitude of its component over the oracle's trace, the form in which test_gpu_prior_source.py
-    holds states above 64 parameters: every step adds an increment that carries the relative error of the adapted factor, so a
-    component that passes through zero keeps an absolute error in proportion to the distances it has moved over, not to its
-    own value."""
-    assert np.array_equal(acc, np.swapaxes(ref["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(ref["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    want = np.swapaxes(ref["theta"][:, 1:], 0, 1)
-    err = np.abs(params - want)
-    print("states: max error / (1e-12 + 1e-9 |state|) %.2e, max error %.2e" % (np.max(err / (1e-12 + 1e-9 * np.abs(want))), np.max(err)))
-    if span_form:
-        span = np.max(np.abs(ref["theta"]), axis=(0, 1))
-        print("states: max error / max(|state|, range of the component) %.2e" % np.max(err / np.maximum(np.abs(want), span)))
-        assert np.all(err <= 1e-9 * np.maximum(np.abs(want), span))
-    else:
-        np.testing.assert_allclose(params, want, rtol=1e-9, atol=1e-12)
 
 
 def span_form_applies(d, prop):
@@ -100,13 +70,7 @@ def test_engine_replays_reference_chain(golden, name, bs):
     params, stats, acc = e.run_host(T1 - 1)
     state = e.proposal_state(want_am=am)
     e.close()
-    assert np.array_equal(acc, np.swapaxes(g["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(g["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(params, np.swapaxes(g["theta"][:, 1:], 0, 1), rtol=1e-9, atol=1e-12)
-    if am:
-        np.testing.assert_allclose(state["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
-    else:
-        np.testing.assert_allclose(state["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
+    compare_replay(params, stats, acc, g, **(dict(C=state["C"]) if am else dict(scaling=state["scaling"])))
     assert_rate(g["accepted"][:, 1:])
 
 
@@ -130,15 +94,10 @@ def test_philox_forward_matches_oracle(shape):
     prop, bs = CASES[shape]
     N, T = 13, 120
     _, y, theta0 = xw.problem(d, m, N, seed=d * 1000 + m)
-    e = make_engine(xw.source(), d, y, N, prop, bs)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    C = e.proposal_state(want_am=True)["C"] if prop["kind"] == "am" else None
-    e.close()
+    params, stats, acc, _, C, z, u = run_forward(make_engine(xw.source(), d, y, N, prop, bs), theta0, T, prop)
     ref = orc.run_mh(level_of(d, m, y), prop, theta0, np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
     assert_rate(ref["accepted"][:, 1:])
-    compare(params, stats, acc, ref, span_form_applies(d, prop))
+    compare(params, stats, acc, ref, span_form=span_form_applies(d, prop))
     if C is not None and d <= 64:  # (above 64 parameters the adapted covariance is the subject of test_gpu_wide.py, not of the model's staging)
         np.testing.assert_allclose(C, ref["C"], rtol=1e-9, atol=1e-14)
 
@@ -177,7 +136,6 @@ def _linear_surrogate(d, m, at):
 def test_hierarchy_matches_oracle(case):
     """wave levels at KSTEPS = 12 / 24 / 48 (base level: tda_user_steps, above: tda_user_level_action), and a hierarchy of a linear
     level, a per-output level and a wave level, against the oracle's Delayed Acceptance / MLDA"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, m, N, seed = 5, 23, 16, 993
@@ -204,24 +162,15 @@ def test_hierarchy_matches_oracle(case):
     set_proposal(e, prop)
     e.set_subchains(sl, False)
     e.init(theta0)
-    rows = e.rows_per_level(n_fine)
-    z, _ = e.set_export(rows[0])
-    outs = e.run_levels_host(n_fine)
-    scal = e.proposal_state()["scaling"]
-    e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, None)
+    rows, z, outs, scal = run_levels_forward(e, n_fine)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, None)
     prior = orc.MVNPrior(np.zeros(d), np.eye(d))
     levels = [orc.CallableGaussianLevel(twins[i], y, "iso", sig[i] ** 2, prior) for i in range(nl)]
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
-    assert_rate(res[nl - 1]["accepted"][:, 1:])
+    assert_rate(res[-1]["accepted"][:, 1:])
     assert_rate(res[0]["accepted"])
     np.testing.assert_allclose(scal, pstate.scaling, rtol=1e-12)
-    for i in range(nl):
-        ref = res[i]
-        sk = slice(1, None) if i == nl - 1 else slice(None)
-        assert np.array_equal(outs[i][2], ref["accepted"][:, sk].T), "level %d accept masks differ" % i
-        np.testing.assert_allclose(outs[i][1][:, :, 2], ref["logpost"][:, sk].T, rtol=1e-10)
-        np.testing.assert_allclose(outs[i][0], np.swapaxes(ref["theta"][:, sk], 0, 1), rtol=1e-9, atol=1e-12)
+    compare_levels(outs, res)
 
 
 # ---- 5. DREAM(Z): jump -> tda_user_eval -> accept ------------------------------------------------------------------------------------
@@ -257,7 +206,6 @@ def test_dreamz_over_the_wave_model():
 # ---- 6. all three source switches in one program ------------------------------------------------------------------------------------
 def test_wave_model_with_source_likelihood_and_source_prior():
     """the wave model + a Student-t DeviceLogLike + a JointPrior of five scipy families under AdaptiveMetropolis"""
-    import tinyda_amd as tda
     from tinyda_amd.engine import Engine
 
     d, m, N, T = 13, 70, 13, 120
@@ -267,16 +215,13 @@ def test_wave_model_with_source_likelihood_and_source_prior():
     truth, theta0 = xp.starts_near_lower_edges(comps, N, rng)
     par = 0.01 * (1.0 + 0.1 * np.arange(m) / m)
     y = xw.np_forward(truth, m)[0] + par * rng.standard_t(4, m)
-    _, p, q, psrc = tda.JointPrior(comps)._source_lowering()
+    p, q, psrc = xp.family_source(comps)
     prop = dict(kind="am", C0=3e-5 * np.eye(d), t0=20, period=20)
     e = Engine(N, d, seed=93, chain_offset=5)
-    e.set_prior_joint(np.full(d, 2), p, q)
-    e.set_level_source(0, xw.source() + xl.KINDS["t"][0] + "\n" + psrc, y, 4, par)
+    e.set_prior_joint(np.full(d, PRIOR_SOURCE), p, q)
+    e.set_level_source(0, xw.source() + xl.KINDS["t"][0] + "\n" + psrc, y, NOISE_SOURCE, par)
     set_proposal(e, prop)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    e.close()
+    params, stats, acc, _, _, z, u = run_forward(e, theta0, T, prop)
     level = xl.LogLikeLevel(lambda th: xw.np_forward(th, m), y, par, xl.KINDS["t"][1], xp.FamilyPrior(comps))
     ref = orc.run_mh(level, prop, theta0, np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
     assert_rate(ref["accepted"][:, 1:])
@@ -303,16 +248,11 @@ def test_mala_matches_oracle(case):
     _, y, theta0 = xw.problem(d, m, N, seed=d * 1000 + m + 1, sigma=MALA_SIGMA)
     prop = dict(kind="mala", scaling=scaling, adaptive=adaptive, gamma=1.01, period=20)
     e = make_engine(xw.source(fwd, grad, m=m), d, y, N, prop, 33, seed=91, chain_offset=3, sigma=MALA_SIGMA, prior=prior)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    scal = e.proposal_state_scaling()
-    e.close()
+    params, stats, acc, scal, _, z, u = run_forward(e, theta0, T, prop)
     level = xw.GradLevel(lambda th: xw.np_forward(th, m), y, "iso", MALA_SIGMA ** 2, orc.MVNPrior(prior[0], np.diag(prior[1])))
     ref = orc.run_mh(level, prop, theta0, np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
     assert_rate(ref["accepted"][:, 1:])
-    compare(params, stats, acc, ref)  # (MALA: rtol 1e-9, atol 1e-12 at every size, as test_gpu_mala_source.py)
-    np.testing.assert_allclose(scal, ref["scaling"], rtol=1e-12)
+    compare(params, stats, acc, ref, scal)  # (MALA: rtol 1e-9, atol 1e-12 at every size, as test_gpu_mala_source.py)
 
 
 # ---- 8. unwritten and NaN outputs ---------------------------------------------------------------------------------------------------
@@ -333,11 +273,7 @@ def test_nan_region_is_rejected():
     _, y, theta0 = xw.problem(d, m, N, seed=5023)
     thr = float(np.max(theta0[:, 0])) + 0.005
     prop = dict(kind="grw", C=1e-3 * np.eye(d), scaling=1.0, adaptive=True, gamma=1.01, period=20)
-    e = make_engine(xw.source(nan_above=thr), d, y, N, prop)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    e.close()
+    params, stats, acc, _, _, z, u = run_forward(make_engine(xw.source(nan_above=thr), d, y, N, prop), theta0, T, prop)
     zs, us = np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1)
     ref = orc.run_mh(level_of(d, m, y, nan_above=thr), prop, theta0, zs, us)
     compare(params, stats, acc, ref)
@@ -357,19 +293,7 @@ def test_checkpoint_resume_is_bitwise():
         e.init(theta0)
         return e
 
-    a = make()
-    whole = a.run_host(90)
-    a.close()
-    b = make()
-    first = b.run_host(37)
-    blob = b.get_state()
-    b.close()
-    c = make()
-    c.set_state(blob)
-    rest = c.run_host(53)
-    c.close()
-    for w, f, r in zip(whole, first, rest):
-        assert np.array_equal(w, np.concatenate([f, r]))
+    assert_resume_bitwise(make)
 
 
 def test_hierarchy_checkpoint_resume_is_bitwise():
@@ -384,15 +308,8 @@ def test_hierarchy_checkpoint_resume_is_bitwise():
     e.set_proposal(0, 1e-3 * np.eye(d), scaling=1.0, adaptive=True, period=10)
     e.set_subchains([3], False)
     e.init(theta0)
-    e.run_levels_host(7)
-    blob = e.get_state()
-    a = e.run_levels_host(9)
-    e.set_state(blob)
-    b = e.run_levels_host(9)
-    e.close()
+    a = assert_levels_resume_bitwise(e)
     assert a[1][2].any()
-    for la, lb in zip(a, b):
-        assert all(np.array_equal(x, y_) for x, y_ in zip(la, lb))
 
 
 # ---- 10. the LDS of a chain is capped at 64 KiB -------------------------------------------------------------------------------------

@@ -15,11 +15,12 @@ import scipy.stats as st
 from oracle import tinyda_oracle as orc
 
 from . import extloglike as xl
+from .extengine import (NOISE_SOURCE, assert_levels_resume_bitwise, assert_rate, assert_resume_bitwise, compare, compare_levels, compare_replay,
+                        oracle_uniforms, run_forward, run_levels_forward, set_proposal)
 from .extmodel import np_forward, source
 
 pytestmark = pytest.mark.gpu
 
-NOISE_SOURCE = 4
 SEED, CHAIN_OFFSET = 91, 3
 
 
@@ -73,14 +74,6 @@ MALA_CASES = {
     "d96_m23_t_mala": (96, 23, "t", dict(kind="mala", scaling=0.025), 0),
 }
 
-PROP_KIND = {"grw": 0, "pcn": 1, "am": 2, "mala": 6}
-
-
-def set_proposal(e, prop):
-    kw = {k: v for k, v in prop.items() if k not in ("kind", "C", "C0")}
-    e.set_proposal(PROP_KIND[prop["kind"]], prop.get("C", prop.get("C0")), **kw)
-
-
 def case_inputs(case, N=13):
     d, m, kind, prop, bs = {**CASES, **MALA_CASES}[case]
     y, par, theta0, pm, pv = problem(d, m, kind, N, seed=d * 1000 + m)
@@ -96,20 +89,6 @@ def make_engine(d, N, src, y, par, pm, pv, prop, bs, n_levels=1, seed=SEED, chai
         e.set_level_source(0, src, y, NOISE_SOURCE, par)
         set_proposal(e, prop)
     return e
-
-
-def compare(params, stats, acc, ref, scal=None):
-    assert np.array_equal(acc, np.swapaxes(ref["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(ref["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(params, np.swapaxes(ref["theta"][:, 1:], 0, 1), rtol=1e-9, atol=1e-12)
-    if scal is not None:
-        np.testing.assert_allclose(scal, ref["scaling"], rtol=1e-12)
-
-
-def assert_rate(accepted):
-    rate = accepted.mean()
-    print("oracle acceptance rate %.3f" % rate)
-    assert 0.1 <= rate <= 0.9, rate
 
 
 # ---- 6. the reference's chains --------------------------------------------------------------------------------------------
@@ -132,14 +111,7 @@ def test_engine_replays_reference_chain(golden, name):
     params, stats, acc = e.run_host(T1 - 1)
     state = e.proposal_state(want_am=kind != "t")
     e.close()
-    assert np.array_equal(acc, np.swapaxes(g["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(g["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(stats[:, :, 1], np.swapaxes(g["loglike"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(params, np.swapaxes(g["theta"][:, 1:], 0, 1), rtol=1e-9, atol=1e-12)
-    if kind == "t":
-        np.testing.assert_allclose(state["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
-    else:
-        np.testing.assert_allclose(state["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
+    compare_replay(params, stats, acc, g, loglike=True, **(dict(scaling=state["scaling"]) if kind == "t" else dict(C=state["C"])))
     assert_rate(g["accepted"][:, 1:])
 
 
@@ -148,13 +120,7 @@ def test_engine_replays_reference_chain(golden, name):
 def test_philox_forward_matches_oracle(case):
     N, T = 13, 120
     d, m, kind, prop, bs, y, par, theta0, pm, pv = case_inputs(case, N)
-    e = make_engine(d, N, full_source(kind), y, par, pm, pv, prop, bs)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    scal = e.proposal_state_scaling()
-    C = e.proposal_state(want_am=True)["C"] if prop["kind"] == "am" else None
-    e.close()
+    params, stats, acc, scal, C, z, u = run_forward(make_engine(d, N, full_source(kind), y, par, pm, pv, prop, bs), theta0, T, prop)
     ref = orc.run_mh(level_of(kind, m, y, par, pm, pv), prop, theta0, np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
     assert_rate(ref["accepted"][:, 1:])
     compare(params, stats, acc, ref, scal)
@@ -207,26 +173,14 @@ def hier_engine(case, N=16, seed=991):
 
 @pytest.mark.parametrize("case", list(HIER))
 def test_hierarchy_matches_oracle(case):
-    from tests.test_gpu_multilevel import _oracle_uniforms
-
     N, seed = 16, 991
     e, sl, n_fine, prop, theta0, levels = hier_engine(case, N, seed)
-    nl = len(levels)
-    rows = e.rows_per_level(n_fine)
-    z, _ = e.set_export(rows[0])
-    outs = e.run_levels_host(n_fine)
-    scal = e.proposal_state()["scaling"]
-    e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, None)
+    rows, z, outs, scal = run_levels_forward(e, n_fine)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, None)
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
-    assert_rate(res[nl - 1]["accepted"][:, 1:])
+    assert_rate(res[-1]["accepted"][:, 1:])  # (the finest level only: the scalings were chosen for it)
     np.testing.assert_allclose(scal, pstate.scaling, rtol=1e-12)
-    for i in range(nl):
-        ref = res[i]
-        sk = slice(1, None) if i == nl - 1 else slice(None)
-        assert np.array_equal(outs[i][2], ref["accepted"][:, sk].T), "level %d accept masks differ" % i
-        np.testing.assert_allclose(outs[i][1][:, :, 2], ref["logpost"][:, sk].T, rtol=1e-10)
-        np.testing.assert_allclose(outs[i][0], np.swapaxes(ref["theta"][:, sk], 0, 1), rtol=1e-9, atol=1e-12)
+    compare_levels(outs, res)
 
 
 # ---- 10. the Gaussian term against the engine's own diagonal noise -------------------------------------------------------------
@@ -282,31 +236,11 @@ def test_checkpoint_resume_is_bitwise(case):
         e.init(theta0)
         return e
 
-    a = make()
-    whole = a.run_host(90)
-    a.close()
-    b = make()
-    first = b.run_host(37)
-    blob = b.get_state()
-    b.close()
-    c = make()
-    c.set_state(blob)
-    rest = c.run_host(53)
-    c.close()
-    for w, f, r in zip(whole, first, rest):
-        assert np.array_equal(w, np.concatenate([f, r]))
+    assert_resume_bitwise(make)
 
 
 def test_hierarchy_checkpoint_resume_is_bitwise():
-    e, *_ = hier_engine("da_t_t_pcn", 12, seed=77)
-    e.run_levels_host(7)
-    blob = e.get_state()
-    a = e.run_levels_host(9)
-    e.set_state(blob)
-    b = e.run_levels_host(9)
-    e.close()
-    for la, lb in zip(a, b):
-        assert all(np.array_equal(x, y_) for x, y_ in zip(la, lb))
+    assert_levels_resume_bitwise(hier_engine("da_t_t_pcn", 12, seed=77)[0])
 
 
 # ---- 13. NaN and -inf terms --------------------------------------------------------------------------------------------------
@@ -323,10 +257,7 @@ def test_nan_and_minus_inf_terms_are_rejected():
     N, T = 13, 120
     d, m, y, par, theta0, pm, pv, nan_f, inf_f, prop = restricted_inputs(N)
     e = make_engine(d, N, source() + xl.restricted_t_source(nan_f, inf_f), y, par, pm, pv, prop, 0)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    e.close()
+    params, stats, acc, _, _, z, u = run_forward(e, theta0, T, prop)
     zz, uu = np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1)
     ref = orc.run_mh(level_of("t", m, y, par, pm, pv, terms=xl.restricted_t_terms(nan_f, inf_f)), prop, theta0, zz, uu)
     assert_rate(ref["accepted"][:, 1:])

@@ -9,6 +9,7 @@ import scipy.stats as st
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import assert_resume_bitwise, compare, compare_replay, run_forward
 from .extmodel import GradLevel, np_forward, source  # the model, its NumPy twin and MALA gradient (tests/extmodel.py)
 from .test_mala_source import FORWARD_ONLY_SRC, ROSEN_SRC
 
@@ -33,10 +34,7 @@ def test_engine_replays_reference_chain(golden):
     params, stats, acc = e.run_host(T1 - 1)
     scal = e.proposal_state_scaling()
     e.close()
-    assert np.array_equal(acc, np.swapaxes(g["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(g["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(params, np.swapaxes(g["theta"][:, 1:], 0, 1), rtol=1e-10, atol=1e-12)
-    np.testing.assert_allclose(scal, g["scaling_hist"][:, -1], rtol=1e-12)
+    compare_replay(params, stats, acc, g, scaling=scal, params_rtol=1e-10)
 
 
 # (the scalings keep the drift theta -> theta + s^2/2 grad contractive: with s^2/2 times the posterior's curvature above 1
@@ -77,18 +75,10 @@ def test_philox_forward_matches_oracle(case):
     d, m, noise, adaptive, scaling, bs = CASES[case]
     N, T = 13, 120
     y, theta0, pm, pv, nz, level = _problem(d, m, noise, N, seed=d * 1000 + m)
-    e = _engine(d, m, noise, N, y, pm, pv, nz, scaling, adaptive, bs)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    scal = e.proposal_state_scaling()
-    e.close()
-    ref = orc.run_mh(level, dict(kind="mala", scaling=scaling, adaptive=adaptive, gamma=1.01, period=20), theta0,
-                     np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
-    assert np.array_equal(acc, np.swapaxes(ref["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(ref["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(params, np.swapaxes(ref["theta"][:, 1:], 0, 1), rtol=1e-9, atol=1e-12)
-    np.testing.assert_allclose(scal, ref["scaling"], rtol=1e-12)
+    prop = dict(kind="mala", scaling=scaling, adaptive=adaptive, gamma=1.01, period=20)
+    params, stats, acc, scal, _, z, u = run_forward(_engine(d, m, noise, N, y, pm, pv, nz, scaling, adaptive, bs), theta0, T, prop)
+    ref = orc.run_mh(level, prop, theta0, np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
+    compare(params, stats, acc, ref, scal)
     assert 0.05 < acc.mean() < 0.98
 
 
@@ -103,19 +93,7 @@ def test_checkpoint_resume_is_bitwise(d):
         e.init(theta0)
         return e
 
-    a = make()
-    whole = a.run_host(90)
-    a.close()
-    b = make()
-    first = b.run_host(37)
-    blob = b.get_state()
-    b.close()
-    c = make()
-    c.set_state(blob)
-    rest = c.run_host(53)
-    c.close()
-    for w, f, r in zip(whole, first, rest):
-        assert np.array_equal(w, np.concatenate([f, r]))
+    assert_resume_bitwise(make)
 
 
 def test_nan_region_is_rejected():

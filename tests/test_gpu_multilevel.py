@@ -5,6 +5,8 @@ import pytest
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import compare_levels, oracle_uniforms
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-10
 KIND = {"grw": 0, "pcn": 1, "am": 2}
@@ -104,17 +106,6 @@ def test_mlda_replay(eng_mod, golden, name, block):
     e.close()
 
 
-def _oracle_uniforms(seed, N, rows, sl, randomize_L=None):
-    ps = orc.PhiloxStream(seed)
-    chains = np.arange(N)
-    us = [np.stack([ps.uniform(chains, t, level=k) for t in range(rows[k])], axis=1) for k in range(len(rows))]
-    ridx = None
-    if randomize_L:
-        x0 = np.stack([ps.words(chains.astype(np.uint32), np.uint32(t), np.uint32(3), np.uint32(0))[0] for t in range(rows[1])], axis=1)
-        ridx = ((x0.astype(np.uint64) * np.uint64(randomize_L)) >> np.uint64(32)).astype(np.float64) - randomize_L
-    return us, ridx
-
-
 @pytest.mark.parametrize("case", ["da_c3", "da_random", "mlda3", "da_long_data", "mlda5", "mlda6"])
 def test_multilevel_philox_forward_vs_oracle(eng_mod, case):
     """Engine on its own Philox stream (normals exported, uniforms / promoted index regenerated bit-exactly by the
@@ -156,14 +147,10 @@ def test_multilevel_philox_forward_vs_oracle(eng_mod, case):
     rows = e.rows_per_level(n_fine)
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, sl[0] if case == "da_random" else None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, sl[0] if case == "da_random" else None)
     prior = orc.MVNPrior(np.zeros(d), np.eye(d))
     levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.01, prior) for k in range(nl)]
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
-    for k in range(nl):
-        ref = res[k]
-        sk = slice(1, None) if k == nl - 1 else slice(None)
-        assert np.array_equal(outs[k][2], ref["accepted"][:, sk].T), "level %d accept masks differ" % k
-        np.testing.assert_allclose(outs[k][1][:, :, 2], ref["logpost"][:, sk].T, rtol=RTOL)
+    compare_levels(outs, res, states=False)
     np.testing.assert_allclose(e.proposal_state()["scaling"], pstate.scaling, rtol=1e-12)
     e.close()

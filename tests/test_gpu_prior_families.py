@@ -11,8 +11,9 @@ from oracle import tinyda_oracle as orc
 
 from . import extfamilies as xf
 from . import extprior as xp
+from .extengine import PRIOR_SOURCE, assert_rate, compare, run_forward
 from .extmodel import np_forward, source
-from .test_gpu_prior_source import PRIOR_SOURCE, SIGMA2, assert_rate, compare, family_source, level_of, make_engine, oracle_proposals_outside
+from .extprior import SIGMA2, family_source, level_of, make_engine, oracle_proposals_outside
 
 pytestmark = pytest.mark.gpu
 
@@ -88,11 +89,7 @@ def test_chains_at_shapes_whose_density_diverges_at_the_edge():
     prior = xp.FamilyPrior(comps)
     assert np.all(prior.inside(theta0))
     prop = dict(kind="grw", C=np.eye(d), scaling=EDGE_SCALING)
-    e = make_engine(comps, N, [(source(), y, 0, SIGMA2)], prop)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    e.close()
+    params, stats, acc, _, _, z, u = run_forward(make_engine(comps, N, [(source(), y, 0, SIGMA2)], prop), theta0, T, prop)
     zz, uu = np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1)
     ref = orc.run_mh(level_of(comps, m, y), prop, theta0, zz, uu)
     assert_rate(ref["accepted"][:, 1:])

@@ -15,22 +15,15 @@ from oracle import tinyda_oracle as orc
 
 from . import extloglike as xl
 from . import extprior as xp
+from .extengine import (NOISE_SOURCE, PRIOR_SOURCE, assert_levels_resume_bitwise, assert_rate, assert_resume_bitwise, compare, compare_levels,
+                        compare_replay, oracle_uniforms, run_forward, run_levels_forward, set_proposal)
 from .extmodel import np_forward, source
+from .extprior import SIGMA2, family_source, level_of, make_engine, oracle_proposals_outside
 from .test_prior_source import _g19_components, g19_oracle_proposal
 
 pytestmark = pytest.mark.gpu
 
-NOISE_SOURCE, PRIOR_SOURCE = 4, 2
-SEED, CHAIN_OFFSET = 93, 5
-SIGMA2 = 0.01
-
-
-def family_source(comps):
-    """(p, q, HIP source of the prior) exactly as sample() hands them over"""
-    import tinyda_amd as tda
-
-    _, p, q, src = tda.JointPrior(comps)._source_lowering()
-    return p, q, src
+SEED, CHAIN_OFFSET = 93, 5  # (extprior.make_engine's defaults, for the engines that are set up by hand below)
 
 
 def problem(d, m, N, seed, names=xp.FAMILY_NAMES, q0=0.15):
@@ -40,70 +33,6 @@ def problem(d, m, N, seed, names=xp.FAMILY_NAMES, q0=0.15):
     truth, theta0 = xp.starts_near_lower_edges(comps, N, rng, q0)
     y = np_forward(truth, m)[0] + np.sqrt(SIGMA2) * rng.standard_normal(m)
     return comps, y, theta0
-
-
-def level_of(comps, m, y, shift=0.0, coup=0.5, noise=("iso", SIGMA2)):
-    return orc.CallableGaussianLevel(lambda th: np_forward(th, m, shift=shift, coup=coup), y, noise[0], noise[1], xp.FamilyPrior(comps))
-
-
-PROP_KIND = {"grw": 0, "am": 2}
-
-
-def set_proposal(e, prop):
-    kw = {k: v for k, v in prop.items() if k not in ("kind", "C", "C0")}
-    e.set_proposal(PROP_KIND[prop["kind"]], prop.get("C", prop.get("C0")), **kw)
-
-
-def make_engine(comps, N, levels, prop, bs=0, seed=SEED, chain_offset=CHAIN_OFFSET, subchains=None):
-    """levels: [(model (+ likelihood) source, data, noise kind, noise)]; the prior is set first, so every level compiles once"""
-    from tinyda_amd.engine import Engine
-
-    p, q, psrc = family_source(comps)
-    e = Engine(N, len(comps), seed=seed, chain_offset=chain_offset, block_steps=bs, n_levels=len(levels))
-    e.set_prior_joint(np.full(len(comps), PRIOR_SOURCE), p, q)
-    for k, (src, y, kind, noise) in enumerate(levels):
-        e.set_level_source(k, src + "\n" + psrc, y, kind, noise)
-    set_proposal(e, prop)
-    if subchains is not None:
-        e.set_subchains(subchains, False)
-    return e
-
-
-def assert_logprior(got, want, theta, prior):
-    """the log-prior is a sum of up to 128 terms of either sign that may cancel (it passes through zero along a chain), so
-    its error is measured against the sum of the terms' magnitudes at the oracle's states: 1e-10 of that, as the log-posterior
-    is held to 1e-10 of itself"""
-    mag = prior.magnitude(theta.reshape(-1, theta.shape[-1])).reshape(want.shape)
-    err = np.abs(got - want)
-    print("log-prior: max error / magnitude %.2e" % np.max(err / mag))
-    assert np.all(err <= 1e-10 * mag), np.max(err / mag)
-
-
-def compare(params, stats, acc, ref, scal=None, prior=None):
-    """masks exact, log-posterior 1e-10; states 1e-9 of themselves (atol 1e-12) up to 64 parameters.  Above 64 parameters a
-    state is held to 1e-9 of the larger of itself and the range of its component over the oracle's trace: every step adds an
-    increment with the relative error of the 128-term proposal sum and of the adapted factor to the state, so a component that
-    passes through zero keeps an absolute error in proportion to the distances it has moved over, not to its own value."""
-    assert np.array_equal(acc, np.swapaxes(ref["accepted"][:, 1:], 0, 1))
-    want = np.swapaxes(ref["theta"][:, 1:], 0, 1)
-    if prior is not None:
-        assert_logprior(stats[:, :, 0], np.swapaxes(ref["logprior"][:, 1:], 0, 1), want, prior)
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(ref["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    if params.shape[-1] > 64:
-        span = np.max(np.abs(ref["theta"]), axis=(0, 1))
-        err = np.abs(params - want)
-        print("states: max error / max(|state|, range of the component) %.2e" % np.max(err / np.maximum(np.abs(want), span)))
-        assert np.all(err <= 1e-9 * np.maximum(np.abs(want), span))
-    else:
-        np.testing.assert_allclose(params, want, rtol=1e-9, atol=1e-12)
-    if scal is not None:
-        np.testing.assert_allclose(scal, ref["scaling"], rtol=1e-12)
-
-
-def assert_rate(accepted):
-    rate = accepted.mean()
-    print("oracle acceptance rate %.3f" % rate)
-    assert 0.1 <= rate <= 0.9, rate
 
 
 # ---- 1. the reference's chains ------------------------------------------------------------------------------------------------
@@ -120,14 +49,7 @@ def test_engine_replays_reference_chain(golden, name):
     params, stats, acc = e.run_host(T1 - 1)
     state = e.proposal_state(want_am=am)
     e.close()
-    assert np.array_equal(acc, np.swapaxes(g["accepted"][:, 1:], 0, 1))
-    np.testing.assert_allclose(stats[:, :, 0], np.swapaxes(g["logprior"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(stats[:, :, 2], np.swapaxes(g["logpost"][:, 1:], 0, 1), rtol=1e-10)
-    np.testing.assert_allclose(params, np.swapaxes(g["theta"][:, 1:], 0, 1), rtol=1e-9, atol=1e-12)
-    if am:
-        np.testing.assert_allclose(state["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
-    else:
-        np.testing.assert_allclose(state["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
+    compare_replay(params, stats, acc, g, logprior=True, **(dict(C=state["C"]) if am else dict(scaling=state["scaling"])))
     assert_rate(g["accepted"][:, 1:])
     assert int(g["n_outside"]) >= 1
 
@@ -158,16 +80,11 @@ def case_inputs(case, N=13):
 def test_philox_forward_matches_oracle(case):
     N, T = 13, 120
     comps, m, prop, bs, theta0, lvl, level = case_inputs(case, N)
-    e = make_engine(comps, N, [lvl], prop, bs)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    scal = e.proposal_state_scaling()
-    C = e.proposal_state(want_am=True)["C"] if prop["kind"] == "am" else None
-    e.close()
+    params, stats, acc, scal, C, z, u = run_forward(make_engine(comps, N, [lvl], prop, bs), theta0, T, prop)
     ref = orc.run_mh(level, prop, theta0, np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1))
     assert_rate(ref["accepted"][:, 1:])
-    compare(params, stats, acc, ref, scal, level.prior)
+    # (above 64 parameters the 128-term proposal sum and the adapted factor put their relative error into every increment)
+    compare(params, stats, acc, ref, scal, prior=level.prior, span_form=params.shape[-1] > 64)
     if C is not None:
         np.testing.assert_allclose(C, ref["C"], rtol=1e-9, atol=1e-14)
 
@@ -196,28 +113,15 @@ def hier_engine(case, N=16, seed=993):
 
 @pytest.mark.parametrize("case", list(HIER))
 def test_hierarchy_matches_oracle(case):
-    from tests.test_gpu_multilevel import _oracle_uniforms
-
     N, seed = 16, 993
     e, sl, n_fine, prop, theta0, levels = hier_engine(case, N, seed)
-    nl = len(levels)
-    rows = e.rows_per_level(n_fine)
-    z, _ = e.set_export(rows[0])
-    outs = e.run_levels_host(n_fine)
-    scal = e.proposal_state()["scaling"]
-    e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, None)
+    rows, z, outs, scal = run_levels_forward(e, n_fine)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, None)
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
-    assert_rate(res[nl - 1]["accepted"][:, 1:])
+    assert_rate(res[-1]["accepted"][:, 1:])
     assert_rate(res[0]["accepted"])
     np.testing.assert_allclose(scal, pstate.scaling, rtol=1e-12)
-    for i in range(nl):
-        ref = res[i]
-        sk = slice(1, None) if i == nl - 1 else slice(None)
-        assert np.array_equal(outs[i][2], ref["accepted"][:, sk].T), "level %d accept masks differ" % i
-        assert_logprior(outs[i][1][:, :, 0], ref["logprior"][:, sk].T, np.swapaxes(ref["theta"][:, sk], 0, 1), levels[i].prior)
-        np.testing.assert_allclose(outs[i][1][:, :, 2], ref["logpost"][:, sk].T, rtol=1e-10)
-        np.testing.assert_allclose(outs[i][0], np.swapaxes(ref["theta"][:, sk], 0, 1), rtol=1e-9, atol=1e-12)
+    compare_levels(outs, res, logprior_of=[level.prior for level in levels])
 
 
 # ---- 4. supports ------------------------------------------------------------------------------------------------------------------
@@ -239,23 +143,12 @@ def support_inputs(N=13):
     return comps, m, y, theta0, prop
 
 
-def oracle_proposals_outside(ref, prior, z, prop):
-    """[N, T] True where the random-walk proposal of step t left a support (fixed scaling, C = I: theta + scaling z)"""
-    props = ref["theta"][:, :-1] + prop["scaling"] * z
-    N, T, d = props.shape
-    return ~prior.inside(props.reshape(-1, d)).reshape(N, T)
-
-
 def test_proposals_outside_the_supports_are_rejected():
     N, T = 13, 120
     comps, m, y, theta0, prop = support_inputs(N)
     prior = xp.FamilyPrior(comps)
     assert np.all(prior.inside(theta0))
-    e = make_engine(comps, N, [(source(), y, 0, SIGMA2)], prop)
-    e.init(theta0)
-    z, u = e.set_export(T)
-    params, stats, acc = e.run_host(T)
-    e.close()
+    params, stats, acc, _, _, z, u = run_forward(make_engine(comps, N, [(source(), y, 0, SIGMA2)], prop), theta0, T, prop)
     zz, uu = np.swapaxes(z, 0, 1), np.swapaxes(u, 0, 1)
     ref = orc.run_mh(level_of(comps, m, y), prop, theta0, zz, uu)
     outside = oracle_proposals_outside(ref, prior, zz, prop)
@@ -363,32 +256,11 @@ def test_checkpoint_resume_is_bitwise(case):
         e.init(theta0)
         return e
 
-    a = make()
-    whole = a.run_host(90)
-    a.close()
-    b = make()
-    first = b.run_host(37)
-    blob = b.get_state()
-    rest_same = b.run_host(53)
-    b.close()
-    c = make()
-    c.set_state(blob)
-    rest = c.run_host(53)
-    c.close()
-    for w, f, r, r2 in zip(whole, first, rest, rest_same):
-        assert np.array_equal(w, np.concatenate([f, r])) and np.array_equal(r, r2)
+    assert_resume_bitwise(make)
 
 
 def test_hierarchy_checkpoint_resume_is_bitwise():
-    e, *_ = hier_engine("da_grw_adaptive", 12, seed=77)
-    e.run_levels_host(7)
-    blob = e.get_state()
-    a = e.run_levels_host(9)
-    e.set_state(blob)
-    b = e.run_levels_host(9)
-    e.close()
-    for la, lb in zip(a, b):
-        assert all(np.array_equal(x, y_) for x, y_ in zip(la, lb))
+    assert_levels_resume_bitwise(hier_engine("da_grw_adaptive", 12, seed=77)[0])
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------------------

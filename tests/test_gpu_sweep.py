@@ -6,6 +6,8 @@ import pytest
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import oracle_uniforms
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10
@@ -129,7 +131,6 @@ def _ml_case(i, wide=False, deep=False):
 def _run_multilevel(i, wide=False, deep=False):
     """one random hierarchy on the device and through the oracle: (case, accept flips over all levels, max relative log-posterior difference)"""
     from tinyda_amd.engine import Engine
-    from tests.test_gpu_multilevel import _oracle_uniforms
 
     c = _ml_case(i, wide, deep)
     nl, d, ms, sl, N, n_fine = c["nl"], c["d"], c["ms"], c["sl"], c["N"], c["n_fine"]
@@ -170,7 +171,7 @@ def _run_multilevel(i, wide=False, deep=False):
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, sl[0] if c["randomize"] else None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, sl[0] if c["randomize"] else None)
     prior = orc.MVNPrior(np.zeros(d), np.eye(d))
     levels = [orc.LinearGaussianLevel(As[k], ys[k], c["noise"], noises[k], prior) for k in range(nl)]
     res, _ = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)

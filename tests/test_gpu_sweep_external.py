@@ -14,6 +14,7 @@ import pytest
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import oracle_uniforms
 from .extmodel import GradLevel, np_forward, np_jacobian, source, weights
 from .test_gpu_sweep import AM_LOOSE_RTOL, RTOL, _small_am, _spd
 
@@ -430,8 +431,6 @@ def _fidelity(k, nl):
 def _run_multilevel(c):
     from tinyda_amd.engine import Engine
 
-    from .test_gpu_multilevel import _oracle_uniforms
-
     nl, d, ms, sl, N, n_fine = c["nl"], c["d"], c["ms"], c["sl"], c["N"], c["n_fine"]
     rng = np.random.default_rng(21000 + c["i"])
     truth = 0.3 * rng.standard_normal(d)
@@ -495,7 +494,7 @@ def _run_multilevel(c):
         pts = truth + (erng.standard_normal((N, d)) @ np.linalg.cholesky(Hinv).T) * 2.0
         ev.append((pts, e.evaluate(pts, level=k)))
     e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, sl[0] if c["randomize"] else None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, sl[0] if c["randomize"] else None)
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
     return levels, outs, res, pstate, scal, ev, rows
 

@@ -6,6 +6,8 @@ import scipy.stats as st
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import compare_levels, oracle_uniforms
+
 pytestmark = pytest.mark.gpu
 
 SRC = """
@@ -165,7 +167,6 @@ def test_source_model_hierarchy_matches_oracle(case):
     """Delayed Acceptance / MLDA with source-defined (hiprtc) models at every level -- no host round trip per step -- and a
     hierarchy mixing a batched host callback (coarse) with a source-defined fine model, against the oracle's DAChain /
     MLDAChain restatement running the NumPy twins of the models."""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, m, N = 5, 23, 21
@@ -206,17 +207,13 @@ def test_source_model_hierarchy_matches_oracle(case):
     outs = e.run_levels_host(n_fine)
     scal = e.proposal_state()["scaling"]
     e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, sl[0] if case == "da_random" else None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, sl[0] if case == "da_random" else None)
     prior = orc.MVNPrior(pm, np.diag(pv))
     nvar = [0.25 ** 2 if (case == "da_linear_coarse" and i == 0) else 0.05 ** 2 for i in range(nl)]
     levels = [orc.CallableGaussianLevel(twins[i], y, "iso", nvar[i], prior) for i in range(nl)]
     res, pstate = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
     np.testing.assert_allclose(scal, pstate.scaling, rtol=1e-12)
-    for i in range(nl):
-        ref = res[i]
-        sk = slice(1, None) if i == nl - 1 else slice(None)
-        assert np.array_equal(outs[i][2], ref["accepted"][:, sk].T), "level %d accept masks differ" % i
-        np.testing.assert_allclose(outs[i][1][:, :, 2], ref["logpost"][:, sk].T, rtol=1e-10)
+    compare_levels(outs, res, states=False)
     assert 0.02 < outs[nl - 1][2].mean() < 0.98
 
 
@@ -243,7 +240,6 @@ def test_hierarchy_with_error_model_matches_oracle(case):
     """State-independent adaptive error model over non-linear models: source-defined levels (DA), and a 3-level MLDA
     hierarchy of a linear surrogate, a batched host callback and a source-defined finest level -- against the oracle's
     restatement of the reference's error-model chains running the NumPy twins."""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, m, N = 5, 23, 17
@@ -296,7 +292,7 @@ def test_hierarchy_with_error_model_matches_oracle(case):
     outs = [tuple(np.concatenate([x1, x2]) for x1, x2 in zip(a1, a2)) for a1, a2 in zip(o1, o2)]
     bias, P = e.error_model_state(0, m)
     e.close()
-    us, _ = _oracle_uniforms(seed, N, rows, sl)
+    us, _ = oracle_uniforms(seed, N, rows, sl)
     prior = orc.MVNPrior(pm, np.diag(pv))
     levels = [dict(fn=twins[i], y=y, prior=prior, **(dict(var=var) if i == nl - 1 else dict(cov=cov))) for i in range(nl)]
     res = orc.run_multilevel_aem(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, aem)
@@ -364,7 +360,6 @@ def test_hierarchy_with_error_model_checkpoint_resume():
 def test_hierarchy_with_uniform_prior_components():
     """JointPrior of uniform and normal components over a Delayed-Acceptance pair of source-defined models, with the error
     model: proposals outside a uniform support are rejected by the base-level kernels; against the oracle."""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, m, N, sl, n_fine = 5, 23, 17, [3], 24
@@ -389,7 +384,7 @@ def test_hierarchy_with_uniform_prior_components():
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, _ = _oracle_uniforms(seed, N, rows, sl)
+    us, _ = oracle_uniforms(seed, N, rows, sl)
     prior = orc.JointPriorOracle(kinds, loc, scale)
     levels = [dict(fn=twins[0], y=y, prior=prior, cov=cov), dict(fn=twins[1], y=y, prior=prior, var=var)]
     res = orc.run_multilevel_aem(levels, dict(kind="grw", C=6e-3 * np.eye(d), scaling=1.0), sl, theta0, np.swapaxes(z, 0, 1), us, n_fine,

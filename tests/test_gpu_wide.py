@@ -6,6 +6,8 @@ import pytest
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import oracle_uniforms
+
 pytestmark = pytest.mark.gpu
 
 
@@ -148,7 +150,6 @@ def test_wide_delayed_acceptance_against_the_oracle(case):
     """Delayed Acceptance and three- / four-level MLDA at 72 .. 128 parameters (generic level kernel k_ml_steps<128, 2..4> + the wide
     proposal / adaptation launches) on the engine's own Philox stream against the oracle: accept masks of every level exact,
     log-posteriors to 1e-10"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, ms, L, N, n_fine, kind = case
@@ -185,7 +186,7 @@ def test_wide_delayed_acceptance_against_the_oracle(case):
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, sl[0] if randomize else None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, sl[0] if randomize else None)
     prior = orc.MVNPrior(np.zeros(d), np.eye(d))
     levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.01, prior) for k in range(nl)]
     res, _ = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
@@ -324,7 +325,6 @@ def test_wide_callback_hierarchy_matches_the_oracle(case):
     k_ext_level_action with a second parameter per lane; mlda_mixed: a LINEAR coarse level beside two callback levels, its outputs
     from k_linear_outputs<128>; da_grw_random: randomised subchain lengths, the promoted state through ysnap) against the oracle
     running the same NumPy models"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, M, N = 90, 40, 17
@@ -375,7 +375,7 @@ def test_wide_callback_hierarchy_matches_the_oracle(case):
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, sl, sl[0] if randomize else None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, sl[0] if randomize else None)
     prior = orc.MVNPrior(pm, np.diag(pv))
     levels = [orc.CallableGaussianLevel(models[k], y, "iso", noise, prior) for k in range(nl)]
     res, _ = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)
@@ -392,7 +392,6 @@ def test_wide_callback_hierarchy_matches_the_oracle(case):
 def test_wide_dense_and_joint_priors_against_the_oracle(case):
     """65 .. 128 parameters under a Gaussian prior with a DENSE covariance (whitening product on the matrix cores, 8 x 8 fragment blocks)
     and under a JointPrior of normal and uniform components (support bounds tested per proposal): single level and hierarchies"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, N = (100 if case.startswith("dense") else 90), 18
@@ -439,7 +438,7 @@ def test_wide_dense_and_joint_priors_against_the_oracle(case):
         z, _ = e.set_export(rows[0])
         outs = e.run_levels_host(n_fine)
         e.close()
-        us, _ = _oracle_uniforms(seed, N, rows, sl)
+        us, _ = oracle_uniforms(seed, N, rows, sl)
         levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.01, prior) for k in range(nl)]
         res, _ = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, None)
         for k in range(nl):
@@ -527,7 +526,6 @@ def _wide_src_twin(shift, coup, m=23):
 def test_wide_source_defined_models_match_the_oracle(case):
     """source-defined (hiprtc-compiled) forward models at 96 parameters: the fused step kernel and the fused level action of the
     compiled module hold two parameters per lane; single level and hierarchies against the oracle running the NumPy twins"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, m, N = 96, 23, 17
@@ -564,7 +562,7 @@ def test_wide_source_defined_models_match_the_oracle(case):
         z, _ = e.set_export(rows[0])
         outs = e.run_levels_host(n_fine)
         e.close()
-        us, _ = _oracle_uniforms(seed, N, rows, sl)
+        us, _ = oracle_uniforms(seed, N, rows, sl)
         res, _ = orc.run_multilevel(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, None)
         for k in range(nl):
             sk = slice(1, None) if k == nl - 1 else slice(None)
@@ -588,7 +586,6 @@ def test_wide_hierarchy_with_error_model_over_external_models(case):
     """the dense error model at 96 parameters over source-defined levels, and over a linear surrogate + a batched host callback + a
     source-defined finest level (k_ext_aem_action / k_ext_aem_accept with the error-model row stride at least 128: a thread is an
     output AND a parameter) -- against the oracle's restatement of the reference's error-model chains running the NumPy twins"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, m, N = 96, 23, 15
@@ -634,7 +631,7 @@ def test_wide_hierarchy_with_error_model_over_external_models(case):
     outs = e.run_levels_host(n_fine)
     bias, P = e.error_model_state(0, m)
     e.close()
-    us, _ = _oracle_uniforms(seed, N, rows, sl)
+    us, _ = oracle_uniforms(seed, N, rows, sl)
     prior = orc.MVNPrior(pm, np.diag(pv))
     levels = [dict(fn=twins[i], y=y, prior=prior, **(dict(var=var) if i == nl - 1 else dict(cov=cov))) for i in range(nl)]
     res = orc.run_multilevel_aem(levels, prop, sl, theta0, np.swapaxes(z, 0, 1), us, n_fine, aem)
@@ -699,8 +696,6 @@ def test_set_proposal_covariance_against_the_oracle(d, when):
 def test_set_proposal_covariance_delayed_acceptance_at_96_parameters():
     """the covariance set after init on a two-level Delayed Acceptance GaussianRandomWalk engine at 96 parameters, against the
     multilevel oracle: accept masks of both levels bit for bit, log-posteriors to 1e-10"""
-    from tests.test_gpu_multilevel import _oracle_uniforms
-
     d, ms, L, N, n_fine = 96, (24, 70), 3, 17, 10
     rng = np.random.default_rng(7300 + d)
     truth = 0.5 * rng.standard_normal(d)
@@ -715,7 +710,7 @@ def test_set_proposal_covariance_delayed_acceptance_at_96_parameters():
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, ridx = _oracle_uniforms(seed, N, rows, [L], None)
+    us, ridx = oracle_uniforms(seed, N, rows, [L], None)
     prior = orc.MVNPrior(np.zeros(d), np.eye(d))
     levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.01, prior) for k in range(2)]
     res, _ = orc.run_multilevel(levels, dict(kind="grw", C=C, scaling=0.8), [L], theta0, np.swapaxes(z, 0, 1), us, n_fine, ridx)

@@ -6,6 +6,8 @@ import scipy.stats as st
 
 from oracle import tinyda_oracle as orc
 
+from .extengine import compare_levels, oracle_uniforms
+
 
 def _components(g):
     return [st.norm(l, s) if k == 0 else st.uniform(l, s) for k, l, s in zip(g["kinds"], g["loc"], g["scale"])]
@@ -80,7 +82,6 @@ def test_linear_hierarchy_and_dreamz_with_uniform_components():
     """The fused multi-level kernel and the DREAM(Z) kernel test the support bounds too: a 3-level MLDA run of linear levels
     against the oracle, and DREAMZ over a linear model staying inside the supports."""
     import tinyda_amd as tda
-    from tests.test_gpu_multilevel import _oracle_uniforms
     from tinyda_amd.engine import Engine
 
     d, N, sl, n_fine, seed = 6, 19, [3, 2], 14, 77
@@ -105,15 +106,12 @@ def test_linear_hierarchy_and_dreamz_with_uniform_components():
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
     e.close()
-    us, _ = _oracle_uniforms(seed, N, rows, sl)
+    us, _ = oracle_uniforms(seed, N, rows, sl)
     prior = orc.JointPriorOracle(kinds, loc, scale)
     levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.04, prior) for k in range(3)]
     res, _ = orc.run_multilevel(levels, dict(kind="am", C0=5e-3 * np.eye(d), t0=20, period=10, adaptive=True, gamma=1.02), sl, theta0,
                                 np.swapaxes(z, 0, 1), us, n_fine, None)
-    for k in range(3):
-        sk = slice(1, None) if k == 2 else slice(None)
-        assert np.array_equal(outs[k][2], res[k]["accepted"][:, sk].T), "level %d accept masks differ" % k
-        np.testing.assert_allclose(outs[k][1][:, :, 2], res[k]["logpost"][:, sk].T, rtol=1e-10)
+    compare_levels(outs, res, states=False)
     assert (outs[0][0][:, :, 0] <= loc[0] + scale[0]).all() and (outs[0][0][:, :, 2] <= loc[2] + scale[2]).all()
     # DREAMZ over a linear model under the same kind of prior
     prior_h = tda.JointPrior([st.uniform(l, s) if k else st.norm(l, s) for k, l, s in zip(kinds, loc, scale)])

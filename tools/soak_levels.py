@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import tinyda_amd.engine as eng_mod
 from oracle import tinyda_oracle as orc
-import tests.test_gpu_multilevel as T
+from tests.extengine import oracle_uniforms
 
 def run(case, n_fine, N):
     rng = np.random.default_rng(78)
@@ -32,7 +32,7 @@ def run(case, n_fine, N):
     rows = e.rows_per_level(n_fine)
     z, _ = e.set_export(rows[0])
     outs = e.run_levels_host(n_fine)
-    us, ridx = T._oracle_uniforms(seed, N, rows, sl, None)
+    us, ridx = oracle_uniforms(seed, N, rows, sl, None)
     prior = orc.MVNPrior(np.zeros(d), np.eye(d))
     levels = [orc.LinearGaussianLevel(As[k], ys[k], "iso", 0.01, prior) for k in range(nl)]
     t0 = time.time()
