@@ -380,10 +380,16 @@ int tda_engine_set_state(tda_engine* e, const void* blob, int64_t bytes);
  * compiled before the prior was set is compiled again by tda_engine_init (and by tda_engine_evaluate), where a source
  * without tda_logprior_term returns TDA_ERR_INVALID naming the signature.  Evaluated inside tda_user_steps of the levels'
  * programs only, so tda_engine_init refuses it with TDA_ERR_UNSUPPORTED wherever another kernel would evaluate the prior or the
- * prior must be Gaussian: a level that is not source-defined or has dense noise, DREAM(Z), pCN, operator-weighted pCN, MALA,
+ * prior must be Gaussian: a level that is not source-defined or has dense noise, DREAM(Z), pCN, operator-weighted pCN,
  * Independence, an error model, randomised subchain lengths, more than four levels; and with TDA_ERR_INVALID without explicit
- * initial parameters.  What is lowered: single-level GRW / AM (dim up to 128; ISO / DIAG noise or TDA_NOISE_SOURCE) and
- * Delayed Acceptance / MLDA of up to four such levels with fixed subchain lengths.  Checkpoint blobs do not record the prior
+ * initial parameters.  What is lowered: single-level GRW / AM (dim up to 128; ISO / DIAG noise or TDA_NOISE_SOURCE),
+ * Delayed Acceptance / MLDA of up to four such levels with fixed subchain lengths, and single-level MALA (TDA_PROP_MALA over a
+ * source with tda_gradient / tda_gradient_wave, as tda_engine_set_level_source has it) when the source also defines the term's
+ * derivative,
+ *     __device__ double tda_logprior_term_grad(double x, double p, double q, int j);   // d term / d x
+ * which the MALA kernels add to the model's vector-Jacobian product in place of the Gaussian prior's gradient.  Its value
+ * outside the support is free: the term is -inf there and the proposal is rejected.  Without the function tda_engine_init
+ * returns TDA_ERR_UNSUPPORTED naming the signature; in a hierarchy MALA stays refused.  Checkpoint blobs do not record the prior
  * (as for every prior): the restoring engine is configured like the saved one.  Priors that couple components are not covered. */
 enum { TDA_PRIOR_NORMAL = 0, TDA_PRIOR_UNIFORM = 1, TDA_PRIOR_SOURCE = 2 }; /* kind[j] of tda_engine_set_prior_joint */
 int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double* loc, const double* scale);
@@ -402,8 +408,9 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
  *     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
  *     // (J(theta)^T sensitivity)_j, 0 <= j < dim -- the reference's model.gradient(parameters, sensitivity)
  * called with the sensitivity Sigma^-1 (y - F(theta)) of all n_outputs outputs; the engine adds the prior's gradient.  Single
- * level, ISO / DIAG noise with m <= 2048, tda_engine_set_prior with a diagonal covariance, dim up to 128.  tda_engine_init
- * compiles the MALA kernels as a second program; a source without tda_gradient returns TDA_ERR_INVALID naming it, JointPrior,
+ * level, ISO / DIAG noise with m <= 2048, tda_engine_set_prior with a diagonal covariance or a source-defined prior with
+ * tda_logprior_term_grad (tda_engine_set_prior_joint), dim up to 128.  tda_engine_init compiles the MALA kernels as a second
+ * program; a source without tda_gradient returns TDA_ERR_INVALID naming it, a JointPrior of normal / uniform components,
  * dense or adaptive noise and more outputs TDA_ERR_UNSUPPORTED.
  * Source-defined likelihood (TDA_NOISE_SOURCE; the reference takes any object with loglike(model_output), posterior.py:95-108):
  * the source defines, after tda_forward, the terms of a separable log-likelihood log L(F) = sum_o term(F_o, y_o, p_o, o),

@@ -62,8 +62,8 @@ def _loglike_source_refusal(low, n_levels, proposal, error_model, randomize):
         return "DeviceLogLike is not lowered with randomize_subchain_length"
     if isinstance(proposal, MALA):
         pc = np.asarray(low["prior_cov"])
-        if n_levels != 1 or "prior_joint" in low or np.count_nonzero(pc - np.diag(np.diag(pc))):
-            return "MALA with a DeviceLogLike: single level, multivariate normal prior with diagonal covariance"
+        if n_levels != 1 or ("prior_joint" in low and "prior_source" not in low) or np.count_nonzero(pc - np.diag(np.diag(pc))):
+            return "MALA with a DeviceLogLike: single level, multivariate normal prior with diagonal covariance or a DevicePrior with its gradient"
         if not low["loglike_has_gradient"]:
             return ("MALA with a DeviceLogLike needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o) "
                     "in the likelihood source")
@@ -86,7 +86,21 @@ def _prior_source_refusal(low, n_levels, proposal, error_model, randomize):
     if isinstance(proposal, (CrankNicolson, OperatorWeightedCrankNicolson)):
         return "%s is not lowered under %s (it needs a Gaussian prior)" % (who, type(proposal).__name__)
     if isinstance(proposal, MALA):
-        return "%s is not lowered under MALA" % who
+        # tda_user_mala_steps takes the prior's gradient from the source: a DevicePrior that defines tda_logprior_term_grad
+        # (DevicePrior.from_distributions for scipy families), single level, over a model with its own gradient
+        if not low["prior_source"]["has_gradient"]:
+            return ("%s is not lowered under MALA: it needs a DevicePrior whose source defines __device__ double "
+                    "tda_logprior_term_grad(double x, double p, double q, int j) (DevicePrior.from_distributions for scipy families)" % who)
+        if n_levels != 1:
+            return "%s under MALA: single level only" % who
+        if not low["has_gradient"]:
+            return ("%s under MALA needs __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, "
+                    "int n_outputs, int j) (or tda_gradient_wave) in the model source" % who)
+        if np.asarray(low["data"]).shape[0] > 2048:
+            return "%s under MALA over a source-defined model: at most 2048 outputs" % who
+        if low["noise_kind"] == _lib.NOISE_SOURCE and not low.get("loglike_has_gradient"):
+            return ("%s under MALA with a DeviceLogLike needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o) "
+                    "in the likelihood source" % who)
     if isinstance(proposal, IndependenceSampler):
         return "%s is not lowered under IndependenceSampler" % who
     if error_model is not None:
@@ -195,9 +209,10 @@ def _device_plan(posteriors, proposal, diagonal_error_model=False, error_model=N
                 return _no("callback / source-defined models need isotropic / diagonal noise (dense: top level only) and a diagonal prior covariance")
     if isinstance(proposal, MALA):
         # exact gradient: of a linear-Gaussian posterior (single level, linear model, Gaussian prior), or from a source-defined
-        # model's own tda_gradient (single level, iso / diag noise, diagonal Gaussian prior: tda_user_mala_steps)
+        # model's own tda_gradient (single level, iso / diag noise, diagonal Gaussian prior or a DevicePrior with its gradient:
+        # tda_user_mala_steps)
         low = lows[0]
-        if len(posteriors) == 1 and "source" in low and "prior_joint" not in low:
+        if len(posteriors) == 1 and "source" in low and ("prior_joint" not in low or "prior_source" in low):  # (a source-defined prior: checked above)
             if not low["has_gradient"]:
                 return _no("MALA over a source-defined model needs __device__ double tda_gradient(const double* theta, int dim, "
                            "const double* sensitivity, int n_outputs, int j) in the model source")

@@ -303,6 +303,7 @@ struct Level {
   std::string usrc;        // the model source (the MALA program is compiled from it at init)
   bool fwd_wave = false, grad_wave = false;  // usrc defines tda_forward_wave / tda_gradient_wave (comments do not count)
   UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0
+  bool uprog_mala_prior = false;  // ... compiled with -DTDA_PRIOR_SOURCE (tda_engine_init rebuilds it when the prior changed since)
   DevBuf<double> udata, uw;
   DevBuf<double> upar;  // TDA_NOISE_SOURCE: the per-output parameters of the source's tda_loglike_term (as given, not inverted)
   double ros_a = 1.0, ros_b = 10.0, ros_data = 0.0;
@@ -336,7 +337,7 @@ struct tda_engine {
   int prior_kind = tda::PRIOR_DIAG;
   bool prior_is_standard = false;  // N(0, I): the single-level tile kernel skips the constant loads
   bool prior_bounded = false;      // JointPrior with uniform components: support bounds in prior_lo / prior_hi
-  bool prior_joint = false;        // set by tda_engine_set_prior_joint (MALA over a source-defined model refuses it)
+  bool prior_joint = false;        // set by tda_engine_set_prior_joint (MALA over a source-defined model takes it all source-defined only)
   bool prior_source = false;       // TDA_PRIOR_SOURCE: tda_logprior_term of the levels' sources; prior_mean / prior_pinv hold its p / q
   double prior_logconst = 0.0;
   std::vector<double> prior_mean_h, prior_cov_h, prior_L_h;

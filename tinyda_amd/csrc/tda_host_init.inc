@@ -17,7 +17,11 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     if (e->is_dreamz) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under DREAM(Z) is not lowered");
     if (e->pp.kind == TDA_PROP_PCN || e->pp.kind == TDA_PROP_OWCN)
       return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under pCN and operator-weighted pCN is not lowered (they need a Gaussian prior)");
-    if (e->pp.kind == TDA_PROP_MALA) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA is not lowered");
+    if (e->pp.kind == TDA_PROP_MALA) {  // tda_user_mala_steps takes the prior's own gradient from the level's source (single level: set_proposal)
+      if (!source_defines(e->levels[0].usrc.c_str(), "tda_logprior_term_grad"))
+        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA needs __device__ double tda_logprior_term_grad(double x, double p, double q, int j) "
+                                         "in the level's source");
+    }
     if (e->pp.kind == TDA_PROP_INDEPENDENCE) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under the Independence proposal is not lowered");
     if (e->aem) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior together with an error model is not lowered");
     if (e->nlev > 1 && e->randomize) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior with randomised subchain lengths is not lowered");
@@ -63,9 +67,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       return fail(TDA_ERR_UNSUPPORTED, "MALA is lowered for linear and source-defined forward models only (exact gradient)");
     if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "MALA needs a Gaussian prior");
     if (l0.noise_kind == TDA_NOISE_ADAPTIVE) return fail(TDA_ERR_UNSUPPORTED, "MALA: adaptive likelihoods are not lowered");
-    if (l0.model == MODEL_USER) {  // tda_user_mala_steps: iso / diag noise, diagonal Gaussian prior, sensitivity of m <= 2048 outputs in LDS
-      if (e->prior_joint || e->prior_kind == PRIOR_DENSE)
-        return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model needs a multivariate normal prior with diagonal covariance");
+    if (l0.model == MODEL_USER) {  // tda_user_mala_steps: iso / diag noise, diagonal Gaussian or source-defined prior, sensitivity of m <= 2048 outputs in LDS
+      if ((e->prior_joint && !e->prior_source) || e->prior_kind == PRIOR_DENSE)
+        return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model needs a multivariate normal prior with diagonal covariance or a source-defined prior");
       if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: isotropic or diagonal noise");
       if (l0.m > 2048) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: at most 2048 outputs");
     }
@@ -263,9 +267,12 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   }
   const bool owcn = !e->is_dreamz && e->pp.kind == TDA_PROP_OWCN, mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA;
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;
-  if (user_mala && !e->levels[0].uprog_mala.mod) {  // the second program: GRW / pCN / AM engines never build it
+  if (user_mala && (!e->levels[0].uprog_mala.mod || e->levels[0].uprog_mala_prior != e->prior_source)) {
+    // the second program: GRW / pCN / AM engines never build it (and a prior that changed kind since builds it again)
     Level& l0 = e->levels[0];
-    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, false, l0.fwd_wave, l0.grad_wave, l0.m, &l0.uprog_mala))) return rc;
+    l0.uprog_mala.unload();
+    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, e->prior_source, l0.fwd_wave, l0.grad_wave, l0.m, &l0.uprog_mala))) return rc;
+    l0.uprog_mala_prior = e->prior_source;
   }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;

@@ -54,3 +54,41 @@ __device__ double tda_logprior_term(double x, double p, double q, int j) {
   }
   return g + tda_prior_c[j];
 }
+// d term / d x = g'(z) / q, which the MALA program needs (tda_user_program.hip, TDA_USER_MALA with TDA_PRIOR_SOURCE); the step
+// programs never call it.  Inside the support only: outside, the term above is -inf and rejects the proposal, and what this
+// function returns there (a NaN of log, a division by zero, a finite number) is never used.
+//   id family        g'(z)
+//    0 norm, 7 halfnorm, 11 truncnorm    -z
+//    1 uniform       0
+//    2 lognorm(s)    (-1 - log z / s^2) / z
+//    3 gamma(a)      (a - 1) / z - 1
+//    4 invgamma(a)   -(a + 1) / z + 1 / z^2               (as (1 / z - (a + 1)) / z: z^2 underflows before 1 / z overflows)
+//    5 beta(a, b)    (a - 1) / z - (b - 1) / (1 - z)
+//    6 expon         -1
+//    8 laplace       -sign z (0 at z = 0)
+//    9 cauchy        -2 z / (1 + z^2)
+//   10 t(nu)         -(nu + 1) z / (nu + z^2)
+//   12 weibull_min(c)   ((c - 1) - c exp(c log z)) / z
+// As above the lanes diverge over the families present, and the one logarithm (families 2 and 12) is taken ahead of the switch.
+__device__ double tda_logprior_term_grad(double x, double p, double q, int j) {
+  const int f = tda_prior_family[j];
+  const double a = tda_prior_a[j], b = tda_prior_b[j];
+  const double z = (x - p) / q;
+  const double lz = ((0x1004 >> f) & 1) ? log(z) : 0.0;
+  double g;
+  switch (f) {
+    case 0: case 7: case 11: g = -z; break;
+    case 1: g = 0.0; break;
+    case 2: g = (-1.0 - lz / (a * a)) / z; break;
+    case 3: g = (a - 1.0) / z - 1.0; break;
+    case 4: g = (1.0 / z - (a + 1.0)) / z; break;
+    case 5: g = (a - 1.0) / z - (b - 1.0) / (1.0 - z); break;
+    case 6: g = -1.0; break;
+    case 8: g = z > 0.0 ? -1.0 : (z < 0.0 ? 1.0 : 0.0); break;
+    case 9: g = -2.0 * z / (1.0 + z * z); break;
+    case 10: g = -(a + 1.0) * z / (a + z * z); break;
+    case 12: g = ((a - 1.0) - a * exp(a * lz)) / z; break;
+    default: g = __builtin_nan(""); break;  // (an id the prologue never writes)
+  }
+  return g / q;
+}

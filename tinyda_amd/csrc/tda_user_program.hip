@@ -21,7 +21,10 @@
 //                         tda_loglike_term_grad, d term / d f.  The Gaussian kinds compile without it.
 //   -DTDA_PRIOR_SOURCE    source-defined prior (tda_engine_set_prior_joint, kind TDA_PRIOR_SOURCE): log p(theta) = sum_j
 //                         tda_logprior_term(theta_j, p_j, q_j, j), defined by the source; the args' `pr_mean` / `pr_pinv` then carry
-//                         p / q as given.  tda_user_steps alone evaluates a prior; the MALA program does not take the switch.
+//                         p / q as given.  tda_user_steps and the MALA kernels evaluate it (the level action carries the log-prior
+//                         of the state it promotes).  MALA also needs tda_logprior_term_grad, d term / d x:
+//     __device__ double tda_logprior_term_grad(double x, double p, double q, int j);
+//                         Outside the support its value is free (NaN, +-inf, anything): the term is -inf there and rejects.
 //   -DTDA_FORWARD_WAVE    the source defines tda_forward_wave: the outputs are taken from LDS (s_out[m], dynamic; the MALA program
 //                         lets the model write into its s_sens[m]) after one call, not from tda_forward(theta, dim, o) per output
 //   -DTDA_GRADIENT_WAVE   (MALA program) the source defines the vector-Jacobian product in the same form, one call for all parameters,
@@ -57,12 +60,12 @@ template <class O>
 __device__ tda_loglike_term_grad_missing tda_loglike_term_grad(double, double, double, O) { return {}; }
 #endif
 #ifdef TDA_PRIOR_SOURCE
-#ifdef TDA_USER_MALA
-#error "TDA_PRIOR_SOURCE: the MALA program knows the diagonal Gaussian prior only"
-#endif
 struct tda_logprior_term_missing {};
 template <class J>
 __device__ tda_logprior_term_missing tda_logprior_term(double, double, double, J) { return {}; }
+struct tda_logprior_term_grad_missing {};
+template <class J>
+__device__ tda_logprior_term_grad_missing tda_logprior_term_grad(double, double, double, J) { return {}; }
 #endif
 
 #include "tda_user_source.h"
@@ -89,6 +92,10 @@ static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_
 #ifdef TDA_PRIOR_SOURCE
 static_assert(!__is_same(decltype(tda_logprior_term(0.0, 0.0, 0.0, 0)), tda_logprior_term_missing),
               "tda_logprior_term_missing: a source-defined prior needs __device__ double tda_logprior_term(double x, double p, double q, int j)");
+#ifdef TDA_USER_MALA
+static_assert(!__is_same(decltype(tda_logprior_term_grad(0.0, 0.0, 0.0, 0)), tda_logprior_term_grad_missing),
+              "tda_logprior_term_grad_missing: MALA under TDA_PRIOR_SOURCE needs __device__ double tda_logprior_term_grad(double x, double p, double q, int j)");
+#endif
 #endif
 
 // The wave forms' LDS: the outputs s_out[m] (dynamic, sized by the host) and the model's workspace.  A program without the
@@ -336,6 +343,13 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int 
 // weighted squares, or the terms of a source-defined likelihood) and leaves the sensitivity in s_sens: grad_loglike =
 // Sigma^-1 (y - F) (distributions.py:300-301 iso: 1 / var * r, :314-315 diag: w * r), or d term / d f
 // (wave form: the model writes its outputs into s_sens, each lane then turns its own entries into sensitivities in place)
+// gradient of the log-prior in parameter j: the source's own under TDA_PRIOR_SOURCE (pm / pinv hold p / q), else the diagonal
+// Gaussian's (utils.py:273-280)
+#if defined(TDA_PRIOR_SOURCE)
+#define TDA_PRIOR_GRAD(x, pm, pinv, j) tda_logprior_term_grad(x, pm, pinv, j)
+#else
+#define TDA_PRIOR_GRAD(x, pm, pinv, j) ((pinv) * ((pm) - (x)))
+#endif
 #ifdef TDA_FORWARD_WAVE
 #define TDA_MALA_OUTPUT(o) s_sens[o]
 #else
@@ -395,6 +409,13 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
     s_th[lane2] = prp2;
     __syncthreads();
     const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, s_work, lane));
+#if defined(TDA_PRIOR_SOURCE)
+    // source-defined prior: the terms summed as tda_user_steps sums them (the same bits for the same state); -inf outside a support
+    double pj = lj ? tda_logprior_term(prp, pm, pinv, lane) : 0.0;
+    if (lj2) pj += tda_logprior_term(prp2, pm2, pinv2, lane2);
+    const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);
+    const double lp_n = tda_wave_sum(pj);  // distributions.py:44-56 (JointPrior.logpdf)
+#else
     double pj = 0.0;
     if (lj) {
       const double dv = prp - pm;
@@ -405,8 +426,9 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
       pj += dv2 * dv2 * pinv2;
     }
     const double maha = tda_wave_sum(pj);
-    const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);
+    const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);  // (in both branches: below the #endif the Gaussian programs lose the instruction order they had)
     const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
+#endif
     const double post_n = lp_n + ll_n;               // link.py:48
 #ifdef TDA_GRADIENT_WAVE
     s_grad[lane] = 0.0;  // (its readers of the previous step are behind the barriers above)
@@ -417,13 +439,19 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
 #ifdef TDA_GRADIENT_WAVE
     tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
     __syncthreads();
-    const double gp = lj ? pinv * (pm - prp) + s_grad[lane] : 0.0;
-    const double gp2 = lj2 ? pinv2 * (pm2 - prp2) + s_grad[lane2] : 0.0;
+    const double gp = lj ? TDA_PRIOR_GRAD(prp, pm, pinv, lane) + s_grad[lane] : 0.0;
+    const double gp2 = lj2 ? TDA_PRIOR_GRAD(prp2, pm2, pinv2, lane2) + s_grad[lane2] : 0.0;
 #else
-    const double gp = lj ? pinv * (pm - prp) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
-    const double gp2 = lj2 ? pinv2 * (pm2 - prp2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+    const double gp = lj ? TDA_PRIOR_GRAD(prp, pm, pinv, lane) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+    const double gp2 = lj2 ? TDA_PRIOR_GRAD(prp2, pm2, pinv2, lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
 #endif
     // transition densities (proposal.py:1000-1005): q(x|y) = -|x - y - s^2/2 grad(y)|^2 / (2 s^2)
+    // A proposal outside a source-defined prior's support is rejected whatever tda_logprior_term_grad returns there (NaN, +-inf):
+    // lp_n is -inf, so post_n - (lp + ll) is -inf or NaN, and a sum that holds a -inf is -inf or NaN whatever is added to it
+    // (kq < 0 and qa >= 0 or NaN: kq * qa is never +inf; kq * qb is finite, gc being the gradient at a state inside the support,
+    // and were it not, -inf + inf is NaN).  alpha is 0 or NaN, `u < NaN` is false, and gc only ever takes an accepted gp.
+    // The first gc is tda_user_mala_grad0's at theta0, which nothing guards: a chain started outside a support has log-prior -inf
+    // and whatever gradient the source returns there, as the host protocol and the oracle have it.
     const double da = (cur - prp) - h * gp, da2 = (cur2 - prp2) - h * gp2;
     const double db = (prp - cur) - h * gc, db2 = (prp2 - cur2) - h * gc2;
     const double qa = tda_wave_sum(da * da + da2 * da2), qb = tda_wave_sum(db * db + db2 * db2);
@@ -487,12 +515,12 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserM
   __syncthreads();
   tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
   __syncthreads();
-  if (lane < a.DP) a.grad[row + lane] = lj ? a.pr_pinv[lane] * (a.pr_mean[lane] - th) + s_grad[lane] : 0.0;
-  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? a.pr_pinv[lane2] * (a.pr_mean[lane2] - th2) + s_grad[lane2] : 0.0;
+  if (lane < a.DP) a.grad[row + lane] = lj ? TDA_PRIOR_GRAD(th, a.pr_mean[lane], a.pr_pinv[lane], lane) + s_grad[lane] : 0.0;
+  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? TDA_PRIOR_GRAD(th2, a.pr_mean[lane2], a.pr_pinv[lane2], lane2) + s_grad[lane2] : 0.0;
 #else
   __syncthreads();
-  if (lane < a.DP) a.grad[row + lane] = lj ? a.pr_pinv[lane] * (a.pr_mean[lane] - th) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
-  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? a.pr_pinv[lane2] * (a.pr_mean[lane2] - th2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+  if (lane < a.DP) a.grad[row + lane] = lj ? TDA_PRIOR_GRAD(th, a.pr_mean[lane], a.pr_pinv[lane], lane) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+  if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? TDA_PRIOR_GRAD(th2, a.pr_mean[lane2], a.pr_pinv[lane2], lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
 #endif
 }
 #endif  // TDA_USER_MALA

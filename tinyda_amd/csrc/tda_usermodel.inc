@@ -83,7 +83,7 @@ int compile_user_program(const char* source, int noise_kind, bool mala, bool pri
   std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   if (noise_kind == TDA_NOISE_SOURCE) opts.push_back("-DTDA_LOGLIKE_SOURCE");
   if (mala) opts.push_back("-DTDA_USER_MALA");
-  if (prior_source) opts.push_back("-DTDA_PRIOR_SOURCE");  // (never together with MALA: tda_engine_init refuses that)
+  if (prior_source) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines tda_logprior_term_grad too)
   if (forward_wave) opts.push_back("-DTDA_FORWARD_WAVE");
   if (gradient_wave) opts.push_back("-DTDA_GRADIENT_WAVE");  // (the MALA program only: the step program calls no gradient)
   if (hiprtcCompileProgram(prog, (int)opts.size(), opts.data()) != HIPRTC_SUCCESS) {
@@ -113,6 +113,9 @@ int compile_user_program(const char* source, int noise_kind, bool mala, bool pri
                                    "double y, double p, int o)");
     if (!mala && log.find("tda_loglike_term_missing") != std::string::npos)
       return fail(TDA_ERR_INVALID, "a source-defined likelihood: the source defines no __device__ double tda_loglike_term(double f, double y, double p, int o)");
+    if (mala && log.find("tda_logprior_term_grad_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "a source-defined prior under MALA: the source defines no __device__ double tda_logprior_term_grad(double x, double p, "
+                                   "double q, int j)");
     if (log.find("tda_logprior_term_missing") != std::string::npos)
       return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines no __device__ double tda_logprior_term(double x, double p, double q, int j)");
     if (log.size() > 400) log.resize(400);

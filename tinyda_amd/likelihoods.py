@@ -174,11 +174,23 @@ class DevicePrior:
     (outside the support) rejects the proposal.  Priors that couple parameters are not covered.  It is compiled into the
     programs of the levels' `DeviceModel`s, so it lowers beside such models only (all levels of a hierarchy share it).
 
+    MALA needs the derivative of the term too, which the source may define:
+
+        __device__ double tda_logprior_term_grad(double x, double p, double q, int j);  // d term / d x
+
+    `has_gradient` says whether it does (comments do not count).  Outside the support the function may return anything: the
+    term is -inf there and the proposal is rejected.  With it the prior lowers under MALA beside a single-level `DeviceModel`
+    that has `tda_gradient` / `tda_gradient_wave`.
+
     `reference`, if given, is any object with `logpdf(theta)` (and optionally `rvs` / `ppf`) -- a `JointPrior`, say -- and
     serves the host protocol; `sample()` draws missing initial parameters through its `ppf`, or else from its
-    `rvs(random_state=generator)`."""
+    `rvs(random_state=generator)`.  `reference_gradient(theta)`, if given, returns d log p / d theta in NumPy and becomes
+    `grad_logpdf` (an attribute only then), which the host MALA uses in place of finite differences of `logpdf`.
 
-    def __init__(self, source, dim, p=None, q=None, reference=None):
+    `DevicePrior.from_distributions(distributions)` builds one from frozen scipy.stats components of the families of
+    csrc/tda_prior_families.h, gradient included: the route by which such priors reach MALA on the device."""
+
+    def __init__(self, source, dim, p=None, q=None, reference=None, reference_gradient=None):
         self.source = str(source)
         self.dim = int(dim)
         if self.dim < 1:
@@ -189,9 +201,33 @@ class DevicePrior:
             raise ValueError("p and q must be vectors with one entry per parameter")
         if not (np.all(np.isfinite(self.p)) and np.all(np.isfinite(self.q))):
             raise ValueError("p and q must be finite")
-        if not re.search(r"\btda_logprior_term\s*\(", _strip_comments(self.source)):
+        stripped = _strip_comments(self.source)
+        if not re.search(r"\btda_logprior_term\s*\(", stripped):
             raise ValueError("the source must define __device__ double tda_logprior_term(double x, double p, double q, int j)")
+        self.has_gradient = re.search(r"\btda_logprior_term_grad\s*\(", stripped) is not None
         self.reference = reference
+        self.reference_gradient = reference_gradient
+        if reference_gradient is not None:
+            self.grad_logpdf = self._reference_gradient  # (an attribute only then: proposals._grad_log_prior looks for it)
+
+    @classmethod
+    def from_distributions(cls, distributions):
+        """The prior of independent frozen scipy.stats components of the families of csrc/tda_prior_families.h as a DevicePrior:
+        the source is the generated tables plus the shipped library (term and gradient), p / q are loc / scale, `reference` is
+        JointPrior(distributions) and `reference_gradient` the exact NumPy gradient of the same formulas.  ValueError names the
+        first component that is outside the families or does not fit the tables."""
+        distributions = list(distributions)
+        rows = [_family_component(dist) for dist in distributions]
+        for j, row in enumerate(rows):
+            if row is None:
+                raise ValueError("component %d (%s) is not a frozen scipy.stats distribution of the families of csrc/tda_prior_families.h "
+                                 "(%s) with finite shape parameters, or its constant is not finite"
+                                 % (j, getattr(getattr(distributions[j], "dist", None), "name", type(distributions[j]).__name__),
+                                    ", ".join(name for name, _ in _FAMILIES)))
+        if not rows:
+            raise ValueError("no components")
+        return cls(_family_prologue(rows) + family_library_source(), len(rows), [r[4] for r in rows], [r[5] for r in rows],
+                   reference=JointPrior(distributions), reference_gradient=lambda theta: family_gradient(rows, theta))
 
     def _host(self, name):
         fn = getattr(self.reference, name, None)
@@ -208,6 +244,9 @@ class DevicePrior:
 
     def ppf(self, x):
         return self._host("ppf")(x)
+
+    def _reference_gradient(self, x):
+        return np.asarray(self.reference_gradient(np.asarray(x, dtype=np.float64)), dtype=np.float64)
 
     def _source_lowering(self):
         """(kinds, p, q, source) with every kind = PRIOR_SOURCE: what Posterior._lowering hands to the engine"""
@@ -313,6 +352,46 @@ def _family_prologue(rows):
     return ("#define TDA_PRIOR_DIM %d\n" % n + table("int", "tda_prior_family", 0, lambda v: "%d" % v)
             + table("double", "tda_prior_a", 1, lambda v: repr(float(v))) + table("double", "tda_prior_b", 2, lambda v: repr(float(v)))
             + table("double", "tda_prior_c", 3, lambda v: repr(float(v))))
+
+
+def family_gradient(rows, theta):
+    """d log p / d theta of the rows (family id, a, b, c, loc, scale) of _family_component at theta[..., dim]: the NumPy twin of
+    tda_logprior_term_grad in csrc/tda_prior_families.h, g'(z) / scale with z = (theta - loc) / scale, the same formulas in the
+    same order of operations.  Outside a support the value is unspecified (as on the device): the density is -inf there."""
+    theta = np.asarray(theta, dtype=np.float64)
+    fam = np.array([r[0] for r in rows])
+    a, b = np.array([r[1] for r in rows], dtype=np.float64), np.array([r[2] for r in rows], dtype=np.float64)
+    loc, scale = np.array([r[4] for r in rows], dtype=np.float64), np.array([r[5] for r in rows], dtype=np.float64)
+    z = (theta - loc) / scale
+    g = np.full(z.shape, np.nan)
+    with np.errstate(all="ignore"):
+        for f in np.unique(fam):
+            k = fam == f
+            zz, aa, bb = z[..., k], a[k], b[k]
+            if f in (0, 7, 11):
+                v = -zz
+            elif f == 1:
+                v = np.zeros_like(zz)
+            elif f == 2:
+                v = (-1.0 - np.log(zz) / (aa * aa)) / zz
+            elif f == 3:
+                v = (aa - 1.0) / zz - 1.0
+            elif f == 4:
+                v = (1.0 / zz - (aa + 1.0)) / zz
+            elif f == 5:
+                v = (aa - 1.0) / zz - (bb - 1.0) / (1.0 - zz)
+            elif f == 6:
+                v = -np.ones_like(zz)
+            elif f == 8:
+                v = -np.sign(zz)
+            elif f == 9:
+                v = -2.0 * zz / (1.0 + zz * zz)
+            elif f == 10:
+                v = -(aa + 1.0) * zz / (aa + zz * zz)
+            else:
+                v = ((aa - 1.0) - aa * np.exp(aa * np.log(zz))) / zz
+            g[..., k] = v
+    return g / scale
 
 
 def family_library_source():

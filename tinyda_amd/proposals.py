@@ -202,7 +202,11 @@ class OperatorWeightedCrankNicolson(CrankNicolson):
 
 
 def _grad_log_prior(x, prior):
-    """utils.py:273-280 for a frozen scipy multivariate normal (anything with mean / cov); finite differences otherwise."""
+    """utils.py:273-280 for a frozen scipy multivariate normal (anything with mean / cov); the prior's own `grad_logpdf` where
+    it has one (a DevicePrior with reference_gradient); finite differences otherwise."""
+    own = getattr(prior, "grad_logpdf", None)
+    if callable(own):
+        return np.asarray(own(x), dtype=np.float64)
     cov = getattr(prior, "cov", None)
     if cov is None and hasattr(prior, "cov_object"):
         cov = prior.cov_object.covariance

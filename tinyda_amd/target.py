@@ -58,8 +58,11 @@ class Posterior:
                 low = self._lowering_with(np.zeros(kinds.shape[0]), np.eye(kinds.shape[0]))
                 if low is not None:
                     low["prior_joint"] = (kinds, p, q)
+                    # has_gradient: the source defines tda_logprior_term_grad too (MALA).  A JointPrior's lowering stays closed
+                    # under MALA: DevicePrior.from_distributions is the route for scipy families there
                     low["prior_source"] = dict(source=src, p=p, q=q, label="DevicePrior" if isinstance(prior, DevicePrior)
-                                               else "JointPrior of scipy families (source-defined prior)")
+                                               else "JointPrior of scipy families (source-defined prior)",
+                                               has_gradient=isinstance(prior, DevicePrior) and prior.has_gradient)
                     if "source" in low:
                         low["source"] = low["source"] + "\n" + src
                 return low
