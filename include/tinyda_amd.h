@@ -390,7 +390,21 @@ int tda_engine_set_state(tda_engine* e, const void* blob, int64_t bytes);
  * which the MALA kernels add to the model's vector-Jacobian product in place of the Gaussian prior's gradient.  Its value
  * outside the support is free: the term is -inf there and the proposal is rejected.  Without the function tda_engine_init
  * returns TDA_ERR_UNSUPPORTED naming the signature; in a hierarchy MALA stays refused.  Checkpoint blobs do not record the prior
- * (as for every prior): the restoring engine is configured like the saved one.  Priors that couple components are not covered. */
+ * (as for every prior): the restoring engine is configured like the saved one.
+ * Priors that couple components (Cauchy-difference and total-variation priors, hierarchical priors, order constraints): the
+ * source defines the wave form INSTEAD of tda_logprior_term (the engine looks for the identifiers in the comment-stripped source;
+ * a source that defines both forms returns TDA_ERR_INVALID from tda_engine_set_level_source),
+ *     __device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane);
+ * The chain's 64 lanes call it together, once per evaluation, and the engine sums the 64 return values.  theta is the proposal
+ * in LDS, entries at index >= dim are unspecified; p / q are loc / scale in device memory, as given.  Every lane is called,
+ * lanes >= dim included; how the function spreads its terms over the lanes is its own business, the idiom is
+ * for (j = lane; j < dim; j += 64).  The function is pure: no barriers, no workspace, no writes.  A NaN or -inf share rejects the
+ * proposal; an initial state with such a share keeps it as its log-prior.  Everything above applies unchanged: where it is
+ * lowered, every refusal, the recompilation of a level compiled before the prior was set.  MALA needs
+ *     __device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j);   // d log p / d theta_j
+ * called by the lane that owns parameter j (j = lane, and lane + 64 above 64 parameters) with the same theta; without it
+ * tda_engine_init returns TDA_ERR_UNSUPPORTED naming the signature.  A proposal with log-prior -inf is rejected whatever the
+ * function returns there.  A tda_logprior_wave of another signature returns TDA_ERR_INVALID naming this one. */
 enum { TDA_PRIOR_NORMAL = 0, TDA_PRIOR_UNIFORM = 1, TDA_PRIOR_SOURCE = 2 }; /* kind[j] of tda_engine_set_prior_joint */
 int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double* loc, const double* scale);
 

@@ -88,6 +88,9 @@ def _prior_source_refusal(low, n_levels, proposal, error_model, randomize):
     if isinstance(proposal, MALA):
         # tda_user_mala_steps takes the prior's gradient from the source: a DevicePrior that defines tda_logprior_term_grad
         # (DevicePrior.from_distributions for scipy families), single level, over a model with its own gradient
+        if low["prior_source"].get("coupled") and not low["prior_source"]["has_gradient"]:
+            return ("%s is not lowered under MALA: a prior that couples parameters needs __device__ double tda_logprior_grad("
+                    "const double* theta, int dim, const double* p, const double* q, int j) in its source" % who)
         if not low["prior_source"]["has_gradient"]:
             return ("%s is not lowered under MALA: it needs a DevicePrior whose source defines __device__ double "
                     "tda_logprior_term_grad(double x, double p, double q, int j) (DevicePrior.from_distributions for scipy families)" % who)

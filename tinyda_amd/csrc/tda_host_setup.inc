@@ -326,9 +326,14 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
   lv.uprog_mala.unload();
   lv.fwd_wave = source_defines(source, "tda_forward_wave");  // the wave forms: one call per evaluation by the chain's whole wave
   lv.grad_wave = source_defines(source, "tda_gradient_wave");
-  int rc = compile_user_program(source, noise_kind, false, e->prior_source, lv.fwd_wave, false, m, &lv.uprog);
+  // the form of a source-defined prior: the term per parameter, or the wave form of a prior that couples parameters (one of them)
+  lv.prior_wave = source_defines(source, "tda_logprior_wave");
+  lv.prior_grad_wave = source_defines(source, "tda_logprior_grad");
+  if (lv.prior_wave && source_defines(source, "tda_logprior_term"))
+    return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines both tda_logprior_term and tda_logprior_wave (a prior has one form)");
+  int rc = compile_user_program(source, noise_kind, false, e->prior_source, e->prior_source && lv.prior_wave, lv.fwd_wave, false, m, &lv.uprog);
   if (rc) return rc;
-  lv.uprog_prior = e->prior_source;  // (a prior set later: tda_engine_init compiles again, ensure_user_programs)
+  lv.uprog_prior = prior_form(e, lv);  // (a prior set later: tda_engine_init compiles again, ensure_user_programs)
   lv.usrc = source;
   std::vector<double> y(data, data + m), w;
   lv.upar.release();

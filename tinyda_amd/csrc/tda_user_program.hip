@@ -11,7 +11,7 @@
 // theta and out are LDS (out: n_outputs doubles, NaN before the call: an entry left unwritten rejects the proposal), `work` is
 // TDA_WORKSPACE doubles of LDS of the chain's own (a #define of the source; 0 / undefined: null), __syncthreads() inside is legal
 // and a wave barrier (one wave per workgroup).
-// Five compile options select what is built (the file itself never defines them):
+// Six compile options select what is built (the file itself never defines them):
 //   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
 //                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
 //     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
@@ -25,6 +25,14 @@
 //                         of the state it promotes).  MALA also needs tda_logprior_term_grad, d term / d x:
 //     __device__ double tda_logprior_term_grad(double x, double p, double q, int j);
 //                         Outside the support its value is free (NaN, +-inf, anything): the term is -inf there and rejects.
+//   -DTDA_PRIOR_WAVE      (in addition to -DTDA_PRIOR_SOURCE) the prior couples parameters: the source defines the wave form instead of
+//                         the term.  The chain's 64 lanes call it together, once per evaluation, and the engine sums the 64 returns:
+//     __device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane);
+//                         theta is the proposal in LDS (entries at index >= dim are unspecified), p / q the arrays as given (device
+//                         memory).  Every lane is called, lanes >= dim too; how the terms spread over the lanes is the function's own
+//                         business (for (j = lane; j < dim; j += 64)).  Pure: no barriers, no workspace, no writes.  A NaN or -inf
+//                         share rejects.  MALA also needs d log p / d theta_j, called by the lane that owns parameter j:
+//     __device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j);
 //   -DTDA_FORWARD_WAVE    the source defines tda_forward_wave: the outputs are taken from LDS (s_out[m], dynamic; the MALA program
 //                         lets the model write into its s_sens[m]) after one call, not from tda_forward(theta, dim, o) per output
 //   -DTDA_GRADIENT_WAVE   (MALA program) the source defines the vector-Jacobian product in the same form, one call for all parameters,
@@ -67,6 +75,14 @@ struct tda_logprior_term_grad_missing {};
 template <class J>
 __device__ tda_logprior_term_grad_missing tda_logprior_term_grad(double, double, double, J) { return {}; }
 #endif
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+struct tda_logprior_wave_missing {};
+template <class L>
+__device__ tda_logprior_wave_missing tda_logprior_wave(const double*, int, const double*, const double*, L) { return {}; }
+struct tda_logprior_grad_missing {};
+template <class J>
+__device__ tda_logprior_grad_missing tda_logprior_grad(const double*, int, const double*, const double*, J) { return {}; }
+#endif
 
 #include "tda_user_source.h"
 
@@ -89,12 +105,22 @@ static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_
               "tda_loglike_term_grad_missing: MALA needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o)");
 #endif
 #endif
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+static_assert(!__is_same(decltype(tda_logprior_wave((const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, 0)), tda_logprior_wave_missing),
+              "tda_logprior_wave_missing: the wave form of the prior is __device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane)");
+#ifdef TDA_USER_MALA
+static_assert(!__is_same(decltype(tda_logprior_grad((const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, 0)), tda_logprior_grad_missing),
+              "tda_logprior_grad_missing: MALA under TDA_PRIOR_WAVE needs __device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j)");
+#endif
+#endif
 #ifdef TDA_PRIOR_SOURCE
+#if !defined(TDA_PRIOR_WAVE)  // (the wave form stands in for the term and its derivative)
 static_assert(!__is_same(decltype(tda_logprior_term(0.0, 0.0, 0.0, 0)), tda_logprior_term_missing),
               "tda_logprior_term_missing: a source-defined prior needs __device__ double tda_logprior_term(double x, double p, double q, int j)");
 #ifdef TDA_USER_MALA
 static_assert(!__is_same(decltype(tda_logprior_term_grad(0.0, 0.0, 0.0, 0)), tda_logprior_term_grad_missing),
               "tda_logprior_term_grad_missing: MALA under TDA_PRIOR_SOURCE needs __device__ double tda_logprior_term_grad(double x, double p, double q, int j)");
+#endif
 #endif
 #endif
 
@@ -192,6 +218,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
     s_th[lane2] = prp2;
     __syncthreads();
     const double ll_n = tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var, s_out, s_work);
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+    // a prior that couples parameters: one call by the whole wave over the proposal in s_th (nothing writes s_th before the next
+    // step's barrier), the lanes' shares summed; a NaN or -inf share makes the sum NaN or -inf and rejects
+    const double lp_n = tda_wave_sum(tda_logprior_wave(s_th, a.d, a.pr_mean, a.pr_pinv, lane));
+#else
 #ifdef TDA_PRIOR_SOURCE
     // source-defined prior: the sum of the components' terms (pm / pinv hold p / q); a component outside its support is -inf
     double pj = lj ? tda_logprior_term(prp, pm, pinv, lane) : 0.0;
@@ -208,6 +239,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepAr
     }
     const double maha = tda_wave_sum(pj);
     const double lp_n = -0.5 * (a.logconst + maha);  // scipy MVN logpdf, posterior.py:92
+#endif
 #endif
     const double post_n = lp_n + ll_n;               // link.py:48
     bool acc = true;
@@ -345,7 +377,10 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int 
 // (wave form: the model writes its outputs into s_sens, each lane then turns its own entries into sensitivities in place)
 // gradient of the log-prior in parameter j: the source's own under TDA_PRIOR_SOURCE (pm / pinv hold p / q), else the diagonal
 // Gaussian's (utils.py:273-280)
-#if defined(TDA_PRIOR_SOURCE)
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+// (the coupled form reads the whole state: s_th holds the proposal in tda_user_mala_steps, the current state in tda_user_mala_grad0)
+#define TDA_PRIOR_GRAD(x, pm, pinv, j) tda_logprior_grad(s_th, a.d, a.pr_mean, a.pr_pinv, j)
+#elif defined(TDA_PRIOR_SOURCE)
 #define TDA_PRIOR_GRAD(x, pm, pinv, j) tda_logprior_term_grad(x, pm, pinv, j)
 #else
 #define TDA_PRIOR_GRAD(x, pm, pinv, j) ((pinv) * ((pm) - (x)))
@@ -409,7 +444,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
     s_th[lane2] = prp2;
     __syncthreads();
     const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, s_work, lane));
-#if defined(TDA_PRIOR_SOURCE)
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+    // a prior that couples parameters: as tda_user_steps calls and sums it (the same bits for the same state)
+    const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);
+    const double lp_n = tda_wave_sum(tda_logprior_wave(s_th, a.d, a.pr_mean, a.pr_pinv, lane));
+#elif defined(TDA_PRIOR_SOURCE)
     // source-defined prior: the terms summed as tda_user_steps sums them (the same bits for the same state); -inf outside a support
     double pj = lj ? tda_logprior_term(prp, pm, pinv, lane) : 0.0;
     if (lj2) pj += tda_logprior_term(prp2, pm2, pinv2, lane2);
@@ -446,7 +485,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
     const double gp2 = lj2 ? TDA_PRIOR_GRAD(prp2, pm2, pinv2, lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
 #endif
     // transition densities (proposal.py:1000-1005): q(x|y) = -|x - y - s^2/2 grad(y)|^2 / (2 s^2)
-    // A proposal outside a source-defined prior's support is rejected whatever tda_logprior_term_grad returns there (NaN, +-inf):
+    // A proposal outside a source-defined prior's support is rejected whatever tda_logprior_term_grad (tda_logprior_grad) returns there (NaN, +-inf):
     // lp_n is -inf, so post_n - (lp + ll) is -inf or NaN, and a sum that holds a -inf is -inf or NaN whatever is added to it
     // (kq < 0 and qa >= 0 or NaN: kq * qa is never +inf; kq * qb is finite, gc being the gradient at a state inside the support,
     // and were it not, -inf + inf is NaN).  alpha is 0 or NaN, `u < NaN` is false, and gc only ever takes an accepted gp.

@@ -74,7 +74,9 @@ bool source_defines(const char* source, const char* name) {
 // forward_wave / gradient_wave: the source defines tda_forward_wave / tda_gradient_wave (source_defines above); a program with
 // either holds at most 64 KiB of LDS per workgroup (= per chain), static and dynamic together, for `m` outputs.  Static LDS
 // beyond the hardware's 160 KiB does not get as far as a module: the compiler refuses it, and its message becomes the same refusal.
-int compile_user_program(const char* source, int noise_kind, bool mala, bool prior_source, bool forward_wave, bool gradient_wave, int m, UserProgram* out) {
+// prior_wave (with prior_source): the source defines the coupled form of the prior, tda_logprior_wave, instead of the term.
+int compile_user_program(const char* source, int noise_kind, bool mala, bool prior_source, bool prior_wave, bool forward_wave, bool gradient_wave, int m,
+                         UserProgram* out) {
   const char* const headers[] = {source, tda_user_args_text};
   const char* const names[] = {"tda_user_source.h", "tda_user_args.h"};
   hiprtcProgram prog;
@@ -84,6 +86,7 @@ int compile_user_program(const char* source, int noise_kind, bool mala, bool pri
   if (noise_kind == TDA_NOISE_SOURCE) opts.push_back("-DTDA_LOGLIKE_SOURCE");
   if (mala) opts.push_back("-DTDA_USER_MALA");
   if (prior_source) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines tda_logprior_term_grad too)
+  if (prior_wave) opts.push_back("-DTDA_PRIOR_WAVE");  // (beside the switch above: tda_logprior_wave, under MALA tda_logprior_grad too)
   if (forward_wave) opts.push_back("-DTDA_FORWARD_WAVE");
   if (gradient_wave) opts.push_back("-DTDA_GRADIENT_WAVE");  // (the MALA program only: the step program calls no gradient)
   if (hiprtcCompileProgram(prog, (int)opts.size(), opts.data()) != HIPRTC_SUCCESS) {
@@ -113,11 +116,18 @@ int compile_user_program(const char* source, int noise_kind, bool mala, bool pri
                                    "double y, double p, int o)");
     if (!mala && log.find("tda_loglike_term_missing") != std::string::npos)
       return fail(TDA_ERR_INVALID, "a source-defined likelihood: the source defines no __device__ double tda_loglike_term(double f, double y, double p, int o)");
+    if (log.find("tda_logprior_wave_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "a source-defined prior: the source's tda_logprior_wave is not __device__ double tda_logprior_wave(const double* theta, "
+                                   "int dim, const double* p, const double* q, int lane)");
+    if (mala && log.find("tda_logprior_grad_missing") != std::string::npos)
+      return fail(TDA_ERR_INVALID, "a source-defined prior under MALA: the source defines no __device__ double tda_logprior_grad(const double* theta, "
+                                   "int dim, const double* p, const double* q, int j)");
     if (mala && log.find("tda_logprior_term_grad_missing") != std::string::npos)
       return fail(TDA_ERR_INVALID, "a source-defined prior under MALA: the source defines no __device__ double tda_logprior_term_grad(double x, double p, "
                                    "double q, int j)");
     if (log.find("tda_logprior_term_missing") != std::string::npos)
-      return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines no __device__ double tda_logprior_term(double x, double p, double q, int j)");
+      return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines no __device__ double tda_logprior_term(double x, double p, double q, int j)"
+                                   " (or, for a prior that couples parameters, tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane))");
     if (log.size() > 400) log.resize(400);
     return fail(TDA_ERR_INVALID, "the forward-model source does not compile%s: %s", mala ? " with the MALA kernels" : "", log.c_str());
   }

@@ -163,7 +163,7 @@ class DeviceLogLike:
 
 
 class DevicePrior:
-    """A prior of independent components given as HIP source (extension; the reference's JointPrior takes any
+    """A prior given as HIP source: independent components, or one that couples parameters (extension; the reference's JointPrior takes any
     scipy.stats.rv_continuous per parameter and evaluates it in Python, distributions.py:8-56):
     log p(theta) = sum_j term(theta_j, p_j, q_j, j).  The source must define
 
@@ -171,8 +171,24 @@ class DevicePrior:
 
     `p` and `q` hold one value per parameter (a location and a scale, say; zeros / ones when not given) and are passed on as
     given; constants shared by all parameters are literals in the source.  The function is pure.  A term that is NaN or -inf
-    (outside the support) rejects the proposal.  Priors that couple parameters are not covered.  It is compiled into the
-    programs of the levels' `DeviceModel`s, so it lowers beside such models only (all levels of a hierarchy share it).
+    (outside the support) rejects the proposal.  It is compiled into the programs of the levels' `DeviceModel`s, so it lowers
+    beside such models only (all levels of a hierarchy share it).
+
+    A prior that couples parameters (Cauchy-difference and total-variation priors, hierarchical priors, order constraints)
+    defines the wave form INSTEAD of the term (a source with both is a ValueError); `coupled` is then true:
+
+        __device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane);
+
+    The 64 lanes of the chain's wave call it together, once per evaluation, and the engine sums the 64 return values.  `theta`
+    is the proposal (entries at index >= dim are unspecified), `p` / `q` the arrays as given.  Every lane is called, lanes >= dim
+    too; how the function spreads its terms over the lanes is its own business -- the idiom is
+    `for (int j = lane; j < dim; j += 64)`.  It is pure: no barriers, no workspace, no writes.  A NaN or -inf share rejects
+    the proposal.  It lowers wherever the separable form does.  Under MALA it needs
+
+        __device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j);  // d log p / d theta_j
+
+    called by the lane that owns parameter j; `has_gradient` then refers to this function.  A proposal whose log-prior is -inf
+    is rejected whatever it returns there.
 
     MALA needs the derivative of the term too, which the source may define:
 
@@ -202,9 +218,16 @@ class DevicePrior:
         if not (np.all(np.isfinite(self.p)) and np.all(np.isfinite(self.q))):
             raise ValueError("p and q must be finite")
         stripped = _strip_comments(self.source)
-        if not re.search(r"\btda_logprior_term\s*\(", stripped):
-            raise ValueError("the source must define __device__ double tda_logprior_term(double x, double p, double q, int j)")
-        self.has_gradient = re.search(r"\btda_logprior_term_grad\s*\(", stripped) is not None
+        term = re.search(r"\btda_logprior_term\s*\(", stripped) is not None
+        self.coupled = re.search(r"\btda_logprior_wave\s*\(", stripped) is not None
+        if term and self.coupled:
+            raise ValueError("the source defines both tda_logprior_term and tda_logprior_wave: a prior has one form")
+        if not term and not self.coupled:
+            raise ValueError("the source must define __device__ double tda_logprior_term(double x, double p, double q, int j) (or, for a "
+                             "prior that couples parameters, __device__ double tda_logprior_wave(const double* theta, int dim, "
+                             "const double* p, const double* q, int lane))")
+        grad = r"\btda_logprior_grad\s*\(" if self.coupled else r"\btda_logprior_term_grad\s*\("
+        self.has_gradient = re.search(grad, stripped) is not None
         self.reference = reference
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:

@@ -62,7 +62,8 @@ class Posterior:
                     # under MALA: DevicePrior.from_distributions is the route for scipy families there
                     low["prior_source"] = dict(source=src, p=p, q=q, label="DevicePrior" if isinstance(prior, DevicePrior)
                                                else "JointPrior of scipy families (source-defined prior)",
-                                               has_gradient=isinstance(prior, DevicePrior) and prior.has_gradient)
+                                               has_gradient=isinstance(prior, DevicePrior) and prior.has_gradient,
+                                               coupled=bool(getattr(prior, "coupled", False)))
                     if "source" in low:
                         low["source"] = low["source"] + "\n" + src
                 return low
