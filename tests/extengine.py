@@ -16,6 +16,57 @@ def set_proposal(e, prop):
     e.set_proposal(PROP_KIND[prop["kind"]], prop.get("C", prop.get("C0")), **kw)
 
 
+def golden_proposal(g):
+    """the oracle's description of the proposal of a recorded reference chain (tests/golden/g18 .. g23)"""
+    if "C0" in g.files:
+        return dict(kind="am", C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
+    return dict(kind="grw", C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]), period=int(g["period"]))
+
+
+def assert_host_classes_replay(g, post, monkeypatch):
+    """the package's host classes over the recorded variates of a reference chain: every accept decision, the log-posterior of
+    every state, the adapted scaling (GaussianRandomWalk) or covariance (AdaptiveMetropolis) at the end"""
+    import tinyda_amd as tda
+
+    kw = {k: v for k, v in golden_proposal(g).items() if k != "kind"}
+    for c in range(g["theta0"].shape[0]):
+        prop = tda.AdaptiveMetropolis(**kw) if "C0" in kw else tda.GaussianRandomWalk(**kw)
+        prop.setup_proposal(parameters=g["theta0"][c], posterior=post)
+        zs = iter(g["z"][c])
+        monkeypatch.setattr(np.random, "standard_normal", lambda n: next(zs))
+        link = post.create_link(g["theta0"][c])
+        np.testing.assert_allclose(link.posterior, g["logpost"][c, 0], rtol=1e-10)
+        accepted = []
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for s in range(g["z"].shape[1]):
+                cand = post.create_link(prop.make_proposal(link))
+                acc = g["u"][c, s] < prop.get_acceptance(cand, link)
+                if acc:
+                    link = cand
+                accepted.append(acc)
+                prop.adapt(parameters=link.parameters, accepted=accepted)
+                assert acc == bool(g["accepted"][c, s + 1]), (c, s)
+                np.testing.assert_allclose(link.posterior, g["logpost"][c, s + 1], rtol=1e-10)
+        if "C0" in kw:
+            np.testing.assert_allclose(prop.C, g["C_hist"][c, -1], rtol=1e-9, atol=1e-14)
+        else:
+            np.testing.assert_allclose(prop.scaling, g["scaling_hist"][c, -1], rtol=1e-12)
+
+
+def assert_oracle_replays(g, level):
+    """the oracle over `level` on the recorded variates of a reference chain; -> its result"""
+    ref = orc.run_mh(level, golden_proposal(g), g["theta0"], g["z"], g["u"])
+    assert np.array_equal(ref["accepted"], g["accepted"])
+    np.testing.assert_allclose(ref["logpost"], g["logpost"], rtol=1e-10)
+    np.testing.assert_allclose(ref["theta"], g["theta"], rtol=1e-9, atol=1e-12)
+    if "C0" in g.files:
+        np.testing.assert_allclose(ref["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
+    else:
+        np.testing.assert_allclose(ref["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
+    assert 0.1 <= g["accepted"][:, 1:].mean() <= 0.9
+    return ref
+
+
 def assert_rate(accepted):
     """agreement of accept masks says something only where the oracle neither accepts nor rejects nearly everything"""
     rate = accepted.mean()

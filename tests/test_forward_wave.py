@@ -2,9 +2,6 @@
 (tests/extwave.py) and its adjoint, the oracle level over the twin against the reference's own chains
 (tests/golden/g20_wave_*.npz, gen_golden_forward_wave.py), the DeviceModel flags, the lowering rules, and the shipped hiprtc
 program compiled offline for gfx950 with the options the engine would pass."""
-import os
-import re
-
 import numpy as np
 import pytest
 import scipy.stats as st
@@ -14,8 +11,9 @@ from oracle import tinyda_oracle as orc
 from . import extloglike as xl
 from . import extprior as xp
 from . import extwave as xw
-from .test_loglike_source import CSRC, PROGRAM, needs_hipcc
-from .test_prior_source import _compile
+from .extengine import assert_oracle_replays
+from .extprogram import (MALA_KERNELS, PROGRAM, STEP_KERNELS, assembly, assert_switch_is_an_option_only, assert_without_scratch,
+                         compile_program as _compile, needs_hipcc)
 
 G20 = ("g20_wave_grw", "g20_wave_am")
 FORWARD_SIG = "__device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)"
@@ -68,19 +66,8 @@ def test_oracle_level_replays_reference_chain(golden, name):
     m = g["data"].shape[0]
     assert g["theta0"].shape == (4, 5 if name == "g20_wave_grw" else 13) and m == (23 if name == "g20_wave_grw" else 100)
     level = orc.CallableGaussianLevel(lambda t: xw.np_forward(t, m), g["data"], "iso", float(g["sigma2"]), orc.MVNPrior(g["prior_mean"], g["prior_cov"]))
-    if "C0" in g.files:
-        prop = dict(kind="am", C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-    else:
-        prop = dict(kind="grw", C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]), period=int(g["period"]))
-    ref = orc.run_mh(level, prop, g["theta0"], g["z"], g["u"])
-    assert np.array_equal(ref["accepted"], g["accepted"])
-    np.testing.assert_allclose(ref["logpost"], g["logpost"], rtol=1e-10)
-    np.testing.assert_allclose(ref["theta"], g["theta"], rtol=1e-9, atol=1e-12)
-    if "C0" in g.files:
-        np.testing.assert_allclose(ref["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
-    else:
-        np.testing.assert_allclose(ref["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
-    assert g["theta"].shape[1] == 301 and 0.1 <= g["accepted"][:, 1:].mean() <= 0.9
+    assert_oracle_replays(g, level)
+    assert g["theta"].shape[1] == 301
 
 
 # ---- 3. DeviceModel ------------------------------------------------------------------------------------------------------------------
@@ -178,10 +165,6 @@ def test_device_plan_hierarchy_dreamz_and_source_switches():
 
 
 # ---- 5. the hiprtc program with the wave switches, compiled offline as shipped ------------------------------------------------------
-STEP_KERNELS = ("tda_user_steps", "tda_user_level_action", "tda_user_eval")
-MALA_KERNELS = ("tda_user_mala_steps", "tda_user_mala_grad0")
-
-
 def _user_source(name):
     if name == "steps_gauss":
         return xw.source()
@@ -209,13 +192,7 @@ def test_wave_programs_compile_for_gfx950_without_scratch(tmp_path, name):
     """every program holds exactly its kernels, without scratch memory and without spilled vector registers (mala_forward_wave:
     the per-parameter tda_gradient over the trajectory that tda_forward_wave left, its tangent in a column of LDS per lane)"""
     switches, kernels = PROGRAMS[name]
-    rc, log, usage = _compile(tmp_path, name, _user_source(name), switches)
-    assert rc == 0, log[-3000:]
-    assert set(kernels) == set(usage), (usage, log[-2000:])
-    for k in kernels:
-        print(name, k, usage[k])
-    for k in kernels:
-        assert usage[k]["ScratchSize [bytes/lane]"] == 0 and usage[k]["VGPRs Spill"] == 0, (k, usage[k])
+    assert_without_scratch(tmp_path, name, _user_source(name), switches, kernels)
 
 
 @needs_hipcc
@@ -240,18 +217,16 @@ def test_wrong_signatures_fail_with_a_message_naming_the_contract(tmp_path):
 
 def test_program_text_never_defines_the_wave_switches():
     """a source without the wave functions is compiled without the switches, and its programs are what they were: the file and
-    its header never define them, and the one option list of the host code passes each on one line behind its flag"""
-    for f in ("tda_user_program.hip", "tda_user_args.h"):
-        txt = open(os.path.join(CSRC, f)).read()
-        assert not re.search(r"#\s*(define|undef)\s+TDA_(FORWARD|GRADIENT)_WAVE\b", txt), f
+    its header never define them (the host's option list and its scan of the source: tests/test_user_build.py)"""
+    header = assert_switch_is_an_option_only(r"TDA_(FORWARD|GRADIENT)_WAVE\b")
     prog = open(PROGRAM).read()
     assert "#ifdef TDA_FORWARD_WAVE" in prog and "#ifdef TDA_GRADIENT_WAVE" in prog
-    host = open(os.path.join(CSRC, "tda_usermodel.inc")).read()
-    assert host.count("hiprtcCompileProgram(") == 1
-    for flag, switch in (("forward_wave", "TDA_FORWARD_WAVE"), ("gradient_wave", "TDA_GRADIENT_WAVE")):
-        uses = [ln for ln in host.splitlines() if switch in ln]
-        assert len(uses) == 1 and re.search(r"if\s*\(\s*%s\s*\)\s*opts\.push_back\(\"-D%s\"\)" % (flag, switch), uses[0]), uses
-    setup = open(os.path.join(CSRC, "tda_host_setup.inc")).read()
-    assert 'source_defines(source, "tda_forward_wave")' in setup and 'source_defines(source, "tda_gradient_wave")' in setup
-    header = open(os.path.join(os.path.dirname(CSRC), "..", "include", "tinyda_amd.h")).read()
     assert FORWARD_SIG in header and "TDA_WORKSPACE" in header and "64 KiB" in header
+
+
+@needs_hipcc
+def test_step_program_does_not_see_the_gradient_switch(tmp_path):
+    """the step program calls no gradient: its instructions do not change under -DTDA_GRADIENT_WAVE"""
+    from .extmodel import source
+
+    assert assembly(tmp_path, "with", source(), ["TDA_GRADIENT_WAVE"]) == assembly(tmp_path, "without", source(), [])

@@ -222,6 +222,60 @@ def test_evaluate_against_scipy(d, m):
     assert np.array_equal(got, got_before_init)
 
 
+def test_programs_are_built_again_when_the_prior_changes_form():
+    """one engine, the linear source model with the lognormal term and its gradient: the step program goes from the source's
+    prior to the engine's Gaussian code (evaluate under each), then the MALA program from the Gaussian code to the source's prior
+    (init under each, one step).  MALA over a source-defined model takes a Gaussian prior through set_prior only, so the same
+    normal components are set that way for it.  Log-prior and log-likelihood against the NumPy twins at every stage, with the
+    bounds of test_evaluate_against_scipy."""
+    import scipy.stats as st
+
+    from tinyda_amd.engine import Engine
+
+    from .extpriorgrad import LOGNORMAL_GRAD_SRC
+    from .test_gpu_mala_source import _linear_source
+
+    d, m, N = 3, 4, 2
+    rng = np.random.default_rng(12)
+    A = rng.standard_normal((m, d))
+    theta0 = np.exp(0.2 * rng.standard_normal((N, d)))
+    y = theta0[0] @ A.T + np.sqrt(SIGMA2) * rng.standard_normal(m)
+    p, q = 0.1 * np.arange(d), 0.5 + 0.1 * np.arange(d)
+    loc, scale = 1.0 + 0.1 * np.arange(d), 0.5 + 0.25 * np.arange(d)
+    pts = theta0 * np.array([[1.1], [0.9]])
+
+    def check(got, theta, source_prior):
+        if source_prior:
+            terms = xp.lognormal_terms(theta, p, q)
+        else:
+            terms = st.norm(loc, scale).logpdf(theta)
+        level = orc.CallableGaussianLevel(lambda t: t @ A.T, y, "iso", SIGMA2, orc.MVNPrior(loc, np.diag(scale ** 2)))
+        ll = level.evaluate(theta)[1]
+        assert np.all(np.isfinite(terms)) and np.all(np.abs(got[:, 0] - terms.sum(axis=1)) <= 1e-11 * np.abs(terms).sum(axis=1)), (got[:, 0], terms.sum(axis=1))
+        np.testing.assert_allclose(got[:, 1], ll, rtol=1e-11)
+
+    e = Engine(N, d, seed=SEED)
+    try:
+        e.set_prior(np.zeros(d), np.eye(d))
+        e.set_level_source(0, _linear_source(A) + xp.LOGNORMAL_SRC + LOGNORMAL_GRAD_SRC, y, 0, SIGMA2)
+        e.set_prior_joint(np.full(d, PRIOR_SOURCE), p, q)
+        check(e.evaluate(pts), pts, True)
+        e.set_prior_joint(np.zeros(d, dtype=np.int32), loc, scale)  # the step program: the source's term -> the engine's own code
+        check(e.evaluate(pts), pts, False)
+        e.set_prior(loc, np.diag(scale ** 2))
+        e.set_proposal(6, None, scaling=0.05)
+        e.init(theta0)
+        check(e.current()[1], theta0, False)
+        e.set_prior_joint(np.full(d, PRIOR_SOURCE), p, q)  # the MALA program: the engine's own code -> the source's term and gradient
+        e.init(theta0)
+        check(e.current()[1], theta0, True)
+        params, stats, _ = e.run_host(1)
+        check(stats[0], params[0], True)
+        assert np.array_equal(e.current()[0], params[0])
+    finally:
+        e.close()
+
+
 def test_start_outside_a_support_keeps_minus_inf_until_a_move_inside():
     """a chain started outside a support has log-prior -inf (as the host protocol and the DeviceLogLike path keep a -inf
     likelihood): the first proposal inside every support is accepted, whatever its density"""

@@ -1,11 +1,6 @@
 """Source-defined log-likelihoods (DeviceLogLike, TDA_NOISE_SOURCE) without a device: the host methods, the lowering
 rules, the host protocol and the oracle level against the reference's own chains (tests/golden/g18_loglike_*.npz,
 gen_golden_loglike_source.py), and the hiprtc programs assembled and compiled offline for gfx950."""
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import scipy.stats as st
@@ -13,9 +8,10 @@ import scipy.stats as st
 from oracle import tinyda_oracle as orc
 
 from . import extloglike as xl
+from .extengine import assert_host_classes_replay, assert_oracle_replays
 from .extmodel import np_forward, np_vjp, source
+from .extprogram import PROGRAM, assembly, assert_switch_is_an_option_only, assert_without_scratch, compile_program, needs_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G18 = {"g18_loglike_student_grw": "t", "g18_loglike_poisson_am": "poisson"}
 
 
@@ -205,13 +201,6 @@ def test_auto_backend_falls_back_with_one_warning():
 
 
 # ---- 3. host protocol against the reference's chains -----------------------------------------------------------------------
-def _g18_proposal(tda, g, kind):
-    if kind == "t":
-        return tda.GaussianRandomWalk(C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]),
-                                      period=int(g["period"]))
-    return tda.AdaptiveMetropolis(C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-
-
 @pytest.mark.parametrize("name", list(G18))
 def test_host_class_replays_reference_chain(golden, monkeypatch, name):
     import tinyda_amd as tda
@@ -222,27 +211,7 @@ def test_host_class_replays_reference_chain(golden, monkeypatch, name):
     m = g["data"].shape[0]
     model = tda.DeviceModel(source(), m, reference=lambda t: np_forward(t, m)[0])
     post = tda.Posterior(st.multivariate_normal(g["prior_mean"], g["prior_cov"]), _loglike(kind, g["data"], g["par"]), model)
-    for c in range(g["theta0"].shape[0]):
-        prop = _g18_proposal(tda, g, kind)
-        prop.setup_proposal(parameters=g["theta0"][c], posterior=post)
-        zs = iter(g["z"][c])
-        monkeypatch.setattr(np.random, "standard_normal", lambda n: next(zs))
-        link = post.create_link(g["theta0"][c])
-        np.testing.assert_allclose(link.posterior, g["logpost"][c, 0], rtol=1e-10)
-        accepted = []
-        for s in range(g["z"].shape[1]):
-            cand = post.create_link(prop.make_proposal(link))
-            acc = g["u"][c, s] < prop.get_acceptance(cand, link)
-            if acc:
-                link = cand
-            accepted.append(acc)
-            prop.adapt(parameters=link.parameters, accepted=accepted)
-            assert acc == bool(g["accepted"][c, s + 1]), (c, s)
-            np.testing.assert_allclose(link.posterior, g["logpost"][c, s + 1], rtol=1e-10)
-        if kind == "t":
-            np.testing.assert_allclose(prop.scaling, g["scaling_hist"][c, -1], rtol=1e-12)
-        else:
-            np.testing.assert_allclose(prop.C, g["C_hist"][c, -1], rtol=1e-9, atol=1e-14)
+    assert_host_classes_replay(g, post, monkeypatch)
 
 
 # ---- 4. the oracle level (which the GPU tests lean on) against the reference's chains ---------------------------------------
@@ -252,19 +221,7 @@ def test_oracle_level_replays_reference_chain(golden, name):
     kind = G18[name]
     m = g["data"].shape[0]
     level = xl.LogLikeLevel(lambda t: np_forward(t, m), g["data"], g["par"], xl.KINDS[kind][1], orc.MVNPrior(g["prior_mean"], g["prior_cov"]))
-    if kind == "t":
-        prop = dict(kind="grw", C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]), period=int(g["period"]))
-    else:
-        prop = dict(kind="am", C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-    ref = orc.run_mh(level, prop, g["theta0"], g["z"], g["u"])
-    assert np.array_equal(ref["accepted"], g["accepted"])
-    np.testing.assert_allclose(ref["logpost"], g["logpost"], rtol=1e-10)
-    np.testing.assert_allclose(ref["theta"], g["theta"], rtol=1e-9, atol=1e-12)
-    if kind == "t":
-        np.testing.assert_allclose(ref["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
-    else:
-        np.testing.assert_allclose(ref["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
-    assert 0.1 <= g["accepted"][:, 1:].mean() <= 0.9
+    assert_oracle_replays(g, level)
 
 
 def test_oracle_level_gradient_against_differences():
@@ -285,36 +242,6 @@ def test_oracle_level_gradient_against_differences():
 
 
 # ---- 5. the hiprtc programs: the shipped file compiled offline as it stands, with the options the engine passes ---------------
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-CSRC = os.path.join(ROOT, "tinyda_amd", "csrc")
-PROGRAM = os.path.join(CSRC, "tda_user_program.hip")
-
-
-def _compile(tmp_path, name, user_source, loglike, mala):
-    """compile_user_program of tda_usermodel.inc: the user's source is the header tda_user_source.h, the switches are -D options"""
-    inc = tmp_path / name
-    inc.mkdir()
-    (inc / "tda_user_source.h").write_text(user_source)
-    switches = (["-DTDA_LOGLIKE_SOURCE"] if loglike else []) + (["-DTDA_USER_MALA"] if mala else [])
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-ffp-contract=off", "-std=c++17", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", "-I" + str(inc), "-I" + CSRC] + switches
-                       + [PROGRAM, "-o", str(tmp_path / (name + ".out"))],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    usage, fn = {}, None
-    for ln in r.stdout.splitlines():
-        mt = re.search(r"Function Name: (\w+)", ln)
-        if mt:
-            fn = mt.group(1)
-            usage[fn] = {}
-        mt = re.search(r"remark: [^:]*:\d+:\d+:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs): (\d+)", ln) or \
-            re.search(r"\s(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs): (\d+)", ln)
-        if mt and fn:
-            usage[fn][mt.group(1)] = int(mt.group(2))
-    return r.returncode, r.stdout, usage
-
-
-needs_hipcc = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which(HIPCC)), reason="no hipcc")
-
 PROGRAMS = {  # name -> (likelihood kind or None for the Gaussian program, MALA program?, kernels)
     "gauss_steps": (None, False, ("tda_user_steps", "tda_user_level_action", "tda_user_eval")),
     "gauss_mala": (None, True, ("tda_user_mala_steps", "tda_user_mala_grad0")),
@@ -330,38 +257,34 @@ PROGRAMS = {  # name -> (likelihood kind or None for the Gaussian program, MALA 
 def test_programs_compile_for_gfx950_without_scratch(tmp_path, name):
     kind, mala, kernels = PROGRAMS[name]
     user = source() + (xl.KINDS[kind][0] if kind else "")
-    rc, log, usage = _compile(tmp_path, name, user, kind is not None, mala)
-    assert rc == 0, log[-3000:]
-    assert set(kernels) == set(usage), (usage, log[-2000:])  # (each program holds exactly its own kernels)
-    for k in kernels:
-        print(name, k, usage[k])  # (scalar spills into vector lanes are reported, not asserted)
-        assert usage[k]["ScratchSize [bytes/lane]"] == 0 and usage[k]["VGPRs Spill"] == 0, (k, usage[k])
+    assert_without_scratch(tmp_path, name, user, (["TDA_LOGLIKE_SOURCE"] if kind else []) + (["TDA_USER_MALA"] if mala else []), kernels)
 
 
 @needs_hipcc
 def test_missing_functions_fail_with_a_message_naming_the_signature(tmp_path):
-    rc, log, _ = _compile(tmp_path, "no_term", source(), True, False)
+    rc, log, _ = compile_program(tmp_path, "no_term", source(), ["TDA_LOGLIKE_SOURCE"])
     assert rc != 0 and "tda_loglike_term_missing" in log
     assert "__device__ double tda_loglike_term(double f, double y, double p, int o)" in log
-    rc, log, _ = _compile(tmp_path, "no_term_mala", source(), True, True)
+    rc, log, _ = compile_program(tmp_path, "no_term_mala", source(), ["TDA_LOGLIKE_SOURCE", "TDA_USER_MALA"])
     assert rc != 0 and "tda_loglike_term_missing" in log
-    rc, log, _ = _compile(tmp_path, "no_grad", source() + xl.TERM_ONLY_SRC, True, True)
+    rc, log, _ = compile_program(tmp_path, "no_grad", source() + xl.TERM_ONLY_SRC, ["TDA_LOGLIKE_SOURCE", "TDA_USER_MALA"])
     assert rc != 0 and "tda_loglike_term_grad_missing" in log and "tda_loglike_term_missing" not in log
     assert "__device__ double tda_loglike_term_grad(double f, double y, double p, int o)" in log
     # the same source serves the step program, which needs no derivative
-    rc, log, _ = _compile(tmp_path, "term_only_steps", source() + xl.TERM_ONLY_SRC, True, False)
+    rc, log, _ = compile_program(tmp_path, "term_only_steps", source() + xl.TERM_ONLY_SRC, ["TDA_LOGLIKE_SOURCE"])
     assert rc == 0, log[-2000:]
 
 
 def test_gaussian_program_text_is_free_of_the_likelihood_switch():
-    """kinds 0-3 are compiled without the switch: after preprocessing their programs are what they were.  The program file and
-    the header it includes never define TDA_LOGLIKE_SOURCE, and the one place in the host code that builds the option list
-    passes it for TDA_NOISE_SOURCE only."""
-    for f in ("tda_user_program.hip", "tda_user_args.h"):
-        txt = open(os.path.join(CSRC, f)).read()
-        assert not re.search(r"#\s*(define|undef)\s+TDA_LOGLIKE_SOURCE", txt), f
+    """kinds 0-3 are compiled without the switch: the program file and the header it includes never define TDA_LOGLIKE_SOURCE,
+    and one place in the host code talks to hiprtc (its option list: tests/test_user_build.py)"""
+    assert_switch_is_an_option_only("TDA_LOGLIKE_SOURCE")
     assert "#ifdef TDA_LOGLIKE_SOURCE" in open(PROGRAM).read()
-    host = open(os.path.join(CSRC, "tda_usermodel.inc")).read()  # (the only file that talks to hiprtc)
-    assert host.count("hiprtcCompileProgram(") == 1
-    uses = [ln for ln in host.splitlines() if "TDA_LOGLIKE_SOURCE" in ln]
-    assert len(uses) == 1 and re.search(r"if\s*\(\s*noise_kind\s*==\s*TDA_NOISE_SOURCE\s*\).*\"-DTDA_LOGLIKE_SOURCE\"", uses[0]), uses
+
+
+@needs_hipcc
+@pytest.mark.parametrize("mala", [False, True])
+def test_gaussian_programs_do_not_see_a_likelihood_in_the_source(tmp_path, mala):
+    """without -DTDA_LOGLIKE_SOURCE the instructions of a program are the same whether or not its source holds a tda_loglike_term"""
+    switches = ["TDA_USER_MALA"] if mala else []
+    assert assembly(tmp_path, "with_term", source() + xl.STUDENT_T_SRC, switches) == assembly(tmp_path, "without", source(), switches)

@@ -2,9 +2,7 @@
 library against scipy's logpdf, the host methods, the lowering rules, the host protocol and the oracle level against the
 reference's own chains (tests/golden/g19_prior_families_*.npz, gen_golden_prior_source.py), and the hiprtc program
 compiled offline for gfx950 with the prior switch."""
-import os
 import re
-import subprocess
 import warnings
 
 import numpy as np
@@ -15,9 +13,10 @@ from oracle import tinyda_oracle as orc
 
 from . import extloglike as xl
 from . import extprior as xp
+from .extengine import assert_host_classes_replay, assert_oracle_replays, golden_proposal as g19_oracle_proposal  # noqa: F401 (test_gpu_prior_source)
 from .extmodel import np_forward, source
 from .extprior import host_library as _host_library
-from .test_loglike_source import CSRC, HIPCC, PROGRAM, needs_hipcc
+from .extprogram import STEP_KERNELS as KERNELS, assembly, assert_switch_is_an_option_only, assert_without_scratch, compile_program, needs_hipcc
 
 G19 = ("g19_prior_families_grw", "g19_prior_families_am")
 TERM_SIG = "__device__ double tda_logprior_term(double x, double p, double q, int j)"
@@ -344,48 +343,17 @@ def _g19_components(g):
             for j, n in enumerate(g["families"])]
 
 
-def g19_oracle_proposal(g):
-    if "C0" in g.files:
-        return dict(kind="am", C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-    return dict(kind="grw", C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]), period=int(g["period"]))
-
-
 @pytest.mark.parametrize("name", G19)
 def test_host_classes_replay_reference_chain(golden, monkeypatch, name):
     import tinyda_amd as tda
 
     g = golden(name)
-    m, am = g["data"].shape[0], "C0" in g.files
+    m = g["data"].shape[0]
     comps = _g19_components(g)
     post = tda.Posterior(tda.JointPrior(comps), tda.GaussianLogLike(g["data"], float(g["sigma2"]) * np.eye(m)),
                          tda.DeviceModel(source(), m, reference=lambda t: np_forward(t, m)[0]))
     assert post.prior._lowering() is None and len(post.prior._source_lowering()) == 4
-    for c in range(g["theta0"].shape[0]):
-        if am:
-            prop = tda.AdaptiveMetropolis(C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-        else:
-            prop = tda.GaussianRandomWalk(C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]),
-                                          period=int(g["period"]))
-        prop.setup_proposal(parameters=g["theta0"][c], posterior=post)
-        zs = iter(g["z"][c])
-        monkeypatch.setattr(np.random, "standard_normal", lambda n: next(zs))
-        link = post.create_link(g["theta0"][c])
-        np.testing.assert_allclose(link.posterior, g["logpost"][c, 0], rtol=1e-10)
-        accepted = []
-        with np.errstate(divide="ignore", invalid="ignore"):
-            for s in range(g["z"].shape[1]):
-                cand = post.create_link(prop.make_proposal(link))
-                acc = g["u"][c, s] < prop.get_acceptance(cand, link)
-                if acc:
-                    link = cand
-                accepted.append(acc)
-                prop.adapt(parameters=link.parameters, accepted=accepted)
-                assert acc == bool(g["accepted"][c, s + 1]), (c, s)
-                np.testing.assert_allclose(link.posterior, g["logpost"][c, s + 1], rtol=1e-10)
-        if am:
-            np.testing.assert_allclose(prop.C, g["C_hist"][c, -1], rtol=1e-9, atol=1e-14)
-        else:
-            np.testing.assert_allclose(prop.scaling, g["scaling_hist"][c, -1], rtol=1e-12)
+    assert_host_classes_replay(g, post, monkeypatch)
 
 
 @pytest.mark.parametrize("name", G19)
@@ -394,41 +362,12 @@ def test_oracle_level_replays_reference_chain(golden, name):
     m = g["data"].shape[0]
     prior = xp.FamilyPrior(_g19_components(g))
     level = orc.CallableGaussianLevel(lambda t: np_forward(t, m), g["data"], "iso", float(g["sigma2"]), prior)
-    ref = orc.run_mh(level, g19_oracle_proposal(g), g["theta0"], g["z"], g["u"])
-    assert np.array_equal(ref["accepted"], g["accepted"])
-    np.testing.assert_allclose(ref["logpost"], g["logpost"], rtol=1e-10)
-    np.testing.assert_allclose(ref["theta"], g["theta"], rtol=1e-9, atol=1e-12)
-    if "C0" in g.files:
-        np.testing.assert_allclose(ref["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
-    else:
-        np.testing.assert_allclose(ref["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
-    assert 0.1 <= g["accepted"][:, 1:].mean() <= 0.9 and int(g["n_outside"]) >= 1
+    assert_oracle_replays(g, level)
+    assert int(g["n_outside"]) >= 1
     assert np.all(prior.inside(g["theta"].reshape(-1, prior.dim)))
 
 
 # ---- 5. the hiprtc program with the prior switch, compiled offline as shipped ------------------------------------------------
-def _compile(tmp_path, name, user_source, switches):
-    inc = tmp_path / name
-    inc.mkdir()
-    (inc / "tda_user_source.h").write_text(user_source)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-ffp-contract=off", "-std=c++17", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", "-I" + str(inc), "-I" + CSRC] + ["-D" + s for s in switches]
-                       + [PROGRAM, "-o", str(tmp_path / (name + ".out"))], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    usage, fn = {}, None
-    for ln in r.stdout.splitlines():
-        mt = re.search(r"Function Name: (\w+)", ln)
-        if mt:
-            fn = mt.group(1)
-            usage[fn] = {}
-        mt = re.search(r"\s(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs): (\d+)", ln)
-        if mt and fn:
-            usage[fn][mt.group(1)] = int(mt.group(2))
-    return r.returncode, r.stdout, usage
-
-
-KERNELS = ("tda_user_steps", "tda_user_level_action", "tda_user_eval")
-
-
 @needs_hipcc
 @pytest.mark.parametrize("loglike", [False, True])
 def test_prior_program_compiles_for_gfx950_without_scratch(tmp_path, loglike):
@@ -436,36 +375,29 @@ def test_prior_program_compiles_for_gfx950_without_scratch(tmp_path, loglike):
     the shipped library"""
     prior_src = _family_prior(128)._source_lowering()[3]
     user = source() + (xl.KINDS["t"][0] if loglike else "") + "\n" + prior_src
-    rc, log, usage = _compile(tmp_path, "prior", user, ["TDA_PRIOR_SOURCE"] + (["TDA_LOGLIKE_SOURCE"] if loglike else []))
-    assert rc == 0, log[-3000:]
-    assert set(KERNELS) == set(usage), (usage, log[-2000:])
-    for k in KERNELS:
-        print(k, usage[k])
-        assert usage[k]["ScratchSize [bytes/lane]"] == 0 and usage[k]["VGPRs Spill"] == 0, (k, usage[k])
+    assert_without_scratch(tmp_path, "prior", user, ["TDA_PRIOR_SOURCE"] + (["TDA_LOGLIKE_SOURCE"] if loglike else []), KERNELS)
 
 
 @needs_hipcc
 def test_handwritten_prior_compiles_and_missing_function_names_the_signature(tmp_path):
-    rc, log, usage = _compile(tmp_path, "lognormal", source() + xp.LOGNORMAL_SRC, ["TDA_PRIOR_SOURCE"])
+    rc, log, usage = compile_program(tmp_path, "lognormal", source() + xp.LOGNORMAL_SRC, ["TDA_PRIOR_SOURCE"])
     assert rc == 0 and usage["tda_user_steps"]["ScratchSize [bytes/lane]"] == 0, log[-2000:]
-    rc, log, _ = _compile(tmp_path, "no_term", source(), ["TDA_PRIOR_SOURCE"])
+    rc, log, _ = compile_program(tmp_path, "no_term", source(), ["TDA_PRIOR_SOURCE"])
     assert rc != 0 and "tda_logprior_term_missing" in log and TERM_SIG in log
     # the MALA program does not take the switch
-    rc, log, _ = _compile(tmp_path, "mala", source() + xp.LOGNORMAL_SRC, ["TDA_PRIOR_SOURCE", "TDA_USER_MALA"])
+    rc, log, _ = compile_program(tmp_path, "mala", source() + xp.LOGNORMAL_SRC, ["TDA_PRIOR_SOURCE", "TDA_USER_MALA"])
     assert rc != 0 and "TDA_PRIOR_SOURCE" in log
 
 
 def test_program_text_never_defines_the_prior_switch():
-    """without -DTDA_PRIOR_SOURCE the programs are what they were: the file and its header never define the switch, the prior's
-    code sits behind it, and the one option list of the host code passes it for a source-defined prior only"""
-    for f in ("tda_user_program.hip", "tda_user_args.h", "tda_prior_families.h"):
-        txt = open(os.path.join(CSRC, f)).read()
-        assert not re.search(r"#\s*(define|undef)\s+TDA_PRIOR_SOURCE", txt), f
-    prog = open(PROGRAM).read()
-    assert prog.count("#ifdef TDA_PRIOR_SOURCE") == 3  # the fallback template, its static_assert, the prior of tda_user_steps
-    host = open(os.path.join(CSRC, "tda_usermodel.inc")).read()
-    assert host.count("hiprtcCompileProgram(") == 1
-    uses = [ln for ln in host.splitlines() if "TDA_PRIOR_SOURCE" in ln]
-    assert len(uses) == 1 and re.search(r"if\s*\(\s*prior_source\s*\)\s*opts\.push_back\(\"-DTDA_PRIOR_SOURCE\"\)", uses[0]), uses
-    header = open(os.path.join(os.path.dirname(CSRC), "..", "include", "tinyda_amd.h")).read()
+    """without -DTDA_PRIOR_SOURCE the programs are what they were: the file and its headers never define the switch (the host's
+    option list: tests/test_user_build.py)"""
+    header = assert_switch_is_an_option_only("TDA_PRIOR_SOURCE", ("tda_prior_families.h",))
     assert re.search(r"TDA_PRIOR_SOURCE\s*=\s*2", header) and TERM_SIG in header
+
+
+@needs_hipcc
+def test_gaussian_prior_program_does_not_see_a_prior_in_the_source(tmp_path):
+    """the prior's code sits behind the switch: without it the step program's instructions are the same whether or not the
+    source holds a tda_logprior_term"""
+    assert assembly(tmp_path, "with_term", source() + xp.LOGNORMAL_SRC, []) == assembly(tmp_path, "without", source(), [])

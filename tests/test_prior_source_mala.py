@@ -14,8 +14,8 @@ from . import extmodel as xm
 from . import extprior as xp
 from . import extpriorgrad as xg
 from . import extwave as xw
-from .test_loglike_source import needs_hipcc
-from .test_prior_source import _compile, _device_prior, _posterior
+from .extprogram import compile_program as _compile, needs_hipcc
+from .test_prior_source import _device_prior, _posterior
 
 MALA_KERNELS = ("tda_user_mala_steps", "tda_user_mala_grad0")
 

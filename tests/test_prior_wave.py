@@ -4,7 +4,6 @@ against finite differences of their own logpdf, the host protocol and the oracle
 (tests/golden/g23_prior_coupled_*.npz, gen_golden_prior_coupled.py), and the hiprtc programs compiled offline for gfx950 with
 the new switch -- and, without it, to the object they compiled to before."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -17,11 +16,11 @@ from . import extmodel as xm
 from . import extprior as xp
 from . import extpriorwave as xw
 from . import extwave as xwv
-from .test_loglike_source import CSRC, HIPCC, PROGRAM, needs_hipcc
-from .test_prior_source import KERNELS, _compile
+from .extengine import assert_host_classes_replay, assert_oracle_replays, golden_proposal as g23_proposal  # noqa: F401 (test_gpu_prior_wave)
+from .extprogram import (CSRC, MALA_KERNELS, PROGRAM, STEP_KERNELS as KERNELS, assembly, assert_switch_is_an_option_only, assert_without_scratch,
+                         compile_program as _compile, needs_hipcc)
 
 G23 = ("g23_prior_coupled_grw", "g23_prior_coupled_am")
-MALA_KERNELS = ("tda_user_mala_steps", "tda_user_mala_grad0")
 TWINS = {"cauchy": xw.cauchy_difference, "tv": xw.total_variation, "hier": xw.hierarchical, "ordered": xw.ordered}
 
 
@@ -253,47 +252,16 @@ def g23_prior(g):
     return {"cauchy": xw.CauchyDifference, "ordered": xw.Ordered}[name](g["p"], g["q"])
 
 
-def g23_proposal(g):
-    if "C0" in g.files:
-        return dict(kind="am", C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-    return dict(kind="grw", C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]), period=int(g["period"]))
-
-
 @pytest.mark.parametrize("name", G23)
 def test_host_classes_replay_reference_chain(golden, monkeypatch, name):
     import tinyda_amd as tda
 
     g = golden(name)
-    m, am = g["data"].shape[0], "C0" in g.files
+    m = g["data"].shape[0]
     post = tda.Posterior(xw.device_prior(g23_prior(g)), tda.GaussianLogLike(g["data"], float(g["sigma2"]) * np.eye(m)),
                          tda.DeviceModel(xm.source(), m, reference=lambda t: xm.np_forward(t, m)[0]))
     assert post.prior.coupled and len(post.prior._source_lowering()) == 4
-    for c in range(g["theta0"].shape[0]):
-        if am:
-            prop = tda.AdaptiveMetropolis(C0=g["C0"], sd=float(g["sd"]), epsilon=float(g["epsilon"]), t0=int(g["t0"]), period=int(g["period"]))
-        else:
-            prop = tda.GaussianRandomWalk(C=g["C"], scaling=float(g["scaling0"]), adaptive=bool(g["adaptive"]), gamma=float(g["gamma"]),
-                                          period=int(g["period"]))
-        prop.setup_proposal(parameters=g["theta0"][c], posterior=post)
-        zs = iter(g["z"][c])
-        monkeypatch.setattr(np.random, "standard_normal", lambda n: next(zs))
-        link = post.create_link(g["theta0"][c])
-        np.testing.assert_allclose(link.posterior, g["logpost"][c, 0], rtol=1e-10)
-        accepted = []
-        with np.errstate(divide="ignore", invalid="ignore"):
-            for s in range(g["z"].shape[1]):
-                cand = post.create_link(prop.make_proposal(link))
-                acc = g["u"][c, s] < prop.get_acceptance(cand, link)
-                if acc:
-                    link = cand
-                accepted.append(acc)
-                prop.adapt(parameters=link.parameters, accepted=accepted)
-                assert acc == bool(g["accepted"][c, s + 1]), (c, s)
-                np.testing.assert_allclose(link.posterior, g["logpost"][c, s + 1], rtol=1e-10)
-        if am:
-            np.testing.assert_allclose(prop.C, g["C_hist"][c, -1], rtol=1e-9, atol=1e-14)
-        else:
-            np.testing.assert_allclose(prop.scaling, g["scaling_hist"][c, -1], rtol=1e-12)
+    assert_host_classes_replay(g, post, monkeypatch)
 
 
 @pytest.mark.parametrize("name", G23)
@@ -302,16 +270,9 @@ def test_oracle_level_replays_reference_chain(golden, name):
     m = g["data"].shape[0]
     prior = g23_prior(g)
     level = orc.CallableGaussianLevel(lambda t: xm.np_forward(t, m), g["data"], "iso", float(g["sigma2"]), prior)
-    ref = orc.run_mh(level, g23_proposal(g), g["theta0"], g["z"], g["u"])
-    assert np.array_equal(ref["accepted"], g["accepted"])
-    np.testing.assert_allclose(ref["logpost"], g["logpost"], rtol=1e-10)
+    ref = assert_oracle_replays(g, level)
     np.testing.assert_allclose(ref["logprior"], g["logprior"], rtol=1e-10)
-    np.testing.assert_allclose(ref["theta"], g["theta"], rtol=1e-9, atol=1e-12)
-    if "C0" in g.files:
-        np.testing.assert_allclose(ref["C"], g["C_hist"][:, -1], rtol=1e-9, atol=1e-14)
-    else:
-        np.testing.assert_allclose(ref["scaling"], g["scaling_hist"][:, -1], rtol=1e-12)
-    assert 0.1 <= g["accepted"][:, 1:].mean() <= 0.9 and g["theta"].shape[1] <= 201
+    assert g["theta"].shape[1] <= 201
     if str(g["prior"]) == "ordered":  # proposals leave the support, and no recorded state does
         assert int(g["n_outside"]) >= 1 and np.all(prior.inside(g["theta"].reshape(-1, prior.dim)))
 
@@ -335,12 +296,7 @@ def test_wave_prior_programs_compile_for_gfx950_without_scratch(tmp_path, prior,
     msrc, step_sw, mala_sw = MODELS[model]
     user = msrc() + "\n" + SOURCES[prior]()
     for name, switches, kernels in (("steps", step_sw, KERNELS), ("mala", mala_sw + ["TDA_USER_MALA"], MALA_KERNELS)):
-        rc, log, usage = _compile(tmp_path, name, user, ["TDA_PRIOR_SOURCE", "TDA_PRIOR_WAVE"] + switches)
-        assert rc == 0, log[-3000:]
-        assert set(kernels) == set(usage), (usage, log[-2000:])
-        for k in kernels:
-            print(prior, model, k, usage[k])
-            assert usage[k]["ScratchSize [bytes/lane]"] == 0 and usage[k]["VGPRs Spill"] == 0, (k, usage[k])
+        assert_without_scratch(tmp_path, name, user, ["TDA_PRIOR_SOURCE", "TDA_PRIOR_WAVE"] + switches, kernels)
 
 
 @needs_hipcc
@@ -363,20 +319,6 @@ def test_missing_functions_name_their_signatures(tmp_path):
     assert rc == 0 and set(usage) == set(KERNELS), log[-2000:]
 
 
-def _object(tmp_path, name, program_text, user_source, switches):
-    """the device object of `program_text` as the step program of `user_source`; the program is compiled from a file of the
-    shipped name in a directory of its own, named relative to it, so that no path differs between two builds"""
-    inc = tmp_path / name
-    inc.mkdir()
-    (inc / "tda_user_source.h").write_text(user_source)
-    (inc / "tda_user_program.hip").write_text(program_text)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-ffp-contract=off", "-std=c++17", "-c", "-I.", "-I" + CSRC]
-                       + ["-D" + s for s in switches] + ["tda_user_program.hip", "-o", "program.out"], cwd=str(inc), stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    return (inc / "program.out").read_bytes()
-
-
 @needs_hipcc
 @pytest.mark.parametrize("switches", [["TDA_PRIOR_SOURCE"], ["TDA_PRIOR_SOURCE", "TDA_USER_MALA"], []])
 def test_without_the_switch_the_programs_are_the_parent_commits(tmp_path, switches):
@@ -389,28 +331,26 @@ def test_without_the_switch_the_programs_are_the_parent_commits(tmp_path, switch
     from .extpriorgrad import LOGNORMAL_GRAD_SRC
 
     user = xm.source() + xp.LOGNORMAL_SRC + LOGNORMAL_GRAD_SRC
-    mine = _object(tmp_path, "mine", open(PROGRAM).read(), user, switches)
-    parents = _object(tmp_path, "parent", r.stdout, user, switches)
+    for name, text in (("mine", open(PROGRAM).read()), ("parent", r.stdout)):
+        rc, log, _ = _compile(tmp_path, name, user, switches, text)
+        assert rc == 0, log[-3000:]
+    mine, parents = (tmp_path / "mine" / "program.out").read_bytes(), (tmp_path / "parent" / "program.out").read_bytes()
     assert len(mine) > 1000 and mine == parents
 
 
 def test_program_text_never_defines_the_wave_switch():
-    """the file and its header never define the switch; every use of it is behind `#if defined(...)` together with the prior
-    switch (or negated inside it); the one option list of the host code passes it from one line, beside the prior switch's own"""
-    for f in ("tda_user_program.hip", "tda_user_args.h", "tda_prior_families.h", "tda_usermodel.inc"):
-        txt = open(os.path.join(CSRC, f)).read()
-        assert not re.search(r"#\s*(define|undef)\s+TDA_PRIOR_WAVE", txt), f
-    prog = open(PROGRAM).read()
-    uses = [ln for ln in prog.splitlines() if ln.lstrip().startswith("#") and "TDA_PRIOR_WAVE" in ln]
-    assert len(uses) == 6, uses
-    for ln in uses:
-        assert re.match(r"#if defined\(TDA_PRIOR_SOURCE\) && defined\(TDA_PRIOR_WAVE\)$", ln) or ln.startswith("#if !defined(TDA_PRIOR_WAVE)"), ln
-    assert "#ifdef TDA_PRIOR_WAVE" not in prog and prog.count("tda_logprior_wave(s_th, a.d, a.pr_mean, a.pr_pinv, lane)") == 2
-    host = open(os.path.join(CSRC, "tda_usermodel.inc")).read()
-    assert host.count("hiprtcCompileProgram(") == 1
-    uses = [ln for ln in host.splitlines() if "TDA_PRIOR_WAVE" in ln]
-    assert len(uses) == 1 and re.search(r"if\s*\(\s*prior_wave\s*\)\s*opts\.push_back\(\"-DTDA_PRIOR_WAVE\"\)", uses[0]), uses
-    assert "TDA_PRIOR_SOURCE" not in uses[0]
-    header = open(os.path.join(os.path.dirname(CSRC), "..", "include", "tinyda_amd.h")).read()
+    """the file and its headers never define the switch, and the public header does not name it (the host's option list:
+    tests/test_user_build.py)"""
+    header = assert_switch_is_an_option_only("TDA_PRIOR_WAVE", ("tda_prior_families.h", "tda_usermodel.inc", "tda_user_build.h"))
+    assert "#ifdef TDA_PRIOR_WAVE" not in open(PROGRAM).read()
     assert xw.WAVE_SIG in header and xw.GRAD_SIG.split(";")[0] in header and "TDA_PRIOR_WAVE" not in header
     assert "couple components are not covered" not in header
+
+
+@needs_hipcc
+@pytest.mark.parametrize("mala", [False, True])
+def test_the_wave_switch_alone_changes_no_instruction(tmp_path, mala):
+    """every use of the switch is behind the prior switch: a program without -DTDA_PRIOR_SOURCE (the Gaussian prior) has the
+    same instructions with and without -DTDA_PRIOR_WAVE"""
+    switches = ["TDA_USER_MALA"] if mala else []
+    assert assembly(tmp_path, "with", xm.source(), switches + ["TDA_PRIOR_WAVE"]) == assembly(tmp_path, "without", xm.source(), switches)

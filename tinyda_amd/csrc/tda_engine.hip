@@ -299,12 +299,9 @@ struct Level {
     cb_theta_h = cb_F_h = nullptr;
   }
   UserProgram uprog;       // tda_user_steps / tda_user_eval / tda_user_level_action
-  int uprog_prior = 0;  // the prior uprog was compiled with (prior_form below; ensure_user_programs rebuilds it when that changed since)
-  std::string usrc;        // the model source (the MALA program is compiled from it at init)
-  bool fwd_wave = false, grad_wave = false;  // usrc defines tda_forward_wave / tda_gradient_wave (comments do not count)
-  bool prior_wave = false, prior_grad_wave = false;  // usrc defines tda_logprior_wave / tda_logprior_grad: the prior couples parameters
-  UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0
-  int uprog_mala_prior = 0;  // ... the prior it was compiled with (tda_engine_init rebuilds it when that changed since)
+  std::string usrc;        // the model source (the programs are compiled from it: ensure_user_program)
+  UserForms forms;         // the optional functions of the contract that usrc defines
+  UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0 (built at init only when the proposal is MALA)
   DevBuf<double> udata, uw;
   DevBuf<double> upar;  // TDA_NOISE_SOURCE: the per-output parameters of the source's tda_loglike_term (as given, not inverted)
   double ros_a = 1.0, ros_b = 10.0, ros_data = 0.0;
@@ -1115,20 +1112,32 @@ int ext_step(tda_engine* e, const Level& lv, const ExtArgs& xa) {
   return TDA_OK;
 }
 
-// what a level's programs are compiled with for the prior: 0 the engine's own Gaussian / uniform code, 1 the source's
-// tda_logprior_term (-DTDA_PRIOR_SOURCE), 2 its tda_logprior_wave (-DTDA_PRIOR_WAVE beside it)
-inline int prior_form(const tda_engine* e, const Level& lv) { return !e->prior_source ? 0 : lv.prior_wave ? 2 : 1; }
+// what a level's program is to be compiled with now (the prior's form: UserProgramSpec::prior_form)
+UserProgramSpec user_program_spec(const tda_engine* e, const Level& lv, bool mala) {
+  UserProgramSpec s;
+  s.mala = mala;
+  s.loglike_source = lv.noise_kind == TDA_NOISE_SOURCE;
+  s.prior_form = !e->prior_source ? 0 : lv.forms.prior_wave ? 2 : 1;
+  s.forward_wave = lv.forms.forward_wave;
+  s.gradient_wave = mala && lv.forms.gradient_wave;
+  return s;
+}
 
-// A source-defined prior lives in the levels' step programs: a program compiled before the prior was set (or after it changed)
-// is compiled again here, from the source the level keeps.  tda_engine_init and tda_engine_evaluate call this.
+// the step program (or the MALA program) of a source-defined level, compiled from the source the level keeps unless it is there
+// and was compiled with what is wanted now: a prior set or changed after the level builds it again
+int ensure_user_program(tda_engine* e, Level& lv, bool mala) {
+  UserProgram& prog = mala ? lv.uprog_mala : lv.uprog;
+  const UserProgramSpec want = user_program_spec(e, lv, mala);
+  if (prog.mod && prog.spec == want) return TDA_OK;
+  prog.unload();
+  return compile_user_program(lv.usrc.c_str(), want, lv.m, &prog);
+}
+
+// A source-defined prior lives in the levels' step programs.  tda_engine_init and tda_engine_evaluate call this.
 int ensure_user_programs(tda_engine* e) {
-  for (Level& lv : e->levels) {
-    if (!lv.set || lv.model != MODEL_USER || lv.uprog_prior == prior_form(e, lv)) continue;
-    lv.uprog.unload();
-    if (int rc = compile_user_program(lv.usrc.c_str(), lv.noise_kind, false, e->prior_source, e->prior_source && lv.prior_wave, lv.fwd_wave, false, lv.m, &lv.uprog))
-      return rc;
-    lv.uprog_prior = prior_form(e, lv);
-  }
+  for (Level& lv : e->levels)
+    if (lv.set && lv.model == MODEL_USER)
+      if (int rc = ensure_user_program(e, lv, false)) return rc;
   return TDA_OK;
 }
 

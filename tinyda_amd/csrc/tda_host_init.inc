@@ -18,12 +18,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     if (e->pp.kind == TDA_PROP_PCN || e->pp.kind == TDA_PROP_OWCN)
       return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under pCN and operator-weighted pCN is not lowered (they need a Gaussian prior)");
     if (e->pp.kind == TDA_PROP_MALA) {  // tda_user_mala_steps takes the prior's own gradient from the level's source (single level: set_proposal)
-      if (e->levels[0].prior_wave && !e->levels[0].prior_grad_wave)
-        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA needs __device__ double tda_logprior_grad(const double* theta, int dim, "
-                                         "const double* p, const double* q, int j) in the level's source");
-      if (!e->levels[0].prior_wave && !source_defines(e->levels[0].usrc.c_str(), "tda_logprior_term_grad"))
-        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA needs __device__ double tda_logprior_term_grad(double x, double p, double q, int j) "
-                                         "in the level's source");
+      const UserForms& f0 = e->levels[0].forms;
+      if (f0.prior_wave ? !f0.prior_grad : !f0.prior_term_grad)
+        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA needs %s in the level's source", f0.prior_wave ? TDA_SIG_LOGPRIOR_GRAD : TDA_SIG_LOGPRIOR_TERM_GRAD);
     }
     if (e->pp.kind == TDA_PROP_INDEPENDENCE) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under the Independence proposal is not lowered");
     if (e->aem) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior together with an error model is not lowered");
@@ -270,15 +267,8 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   }
   const bool owcn = !e->is_dreamz && e->pp.kind == TDA_PROP_OWCN, mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA;
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;
-  if (user_mala && (!e->levels[0].uprog_mala.mod || e->levels[0].uprog_mala_prior != prior_form(e, e->levels[0]))) {
-    // the second program: GRW / pCN / AM engines never build it (and a prior that changed kind since builds it again)
-    Level& l0 = e->levels[0];
-    l0.uprog_mala.unload();
-    if ((rc = compile_user_program(l0.usrc.c_str(), l0.noise_kind, true, e->prior_source, e->prior_source && l0.prior_wave, l0.fwd_wave, l0.grad_wave, l0.m,
-                                   &l0.uprog_mala)))
-      return rc;
-    l0.uprog_mala_prior = prior_form(e, l0);
-  }
+  // the second program: GRW / pCN / AM engines never build it
+  if (user_mala && (rc = ensure_user_program(e, e->levels[0], true))) return rc;
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;
   const double* Cuse = (e->pp.kind == TDA_PROP_PCN || owcn) ? e->prior_cov_h.data() : e->prop_C_h.data();  // proposal.py:336-341

@@ -324,17 +324,20 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
   Level& lv = e->levels[level];
   lv.uprog.unload();
   lv.uprog_mala.unload();
-  lv.fwd_wave = source_defines(source, "tda_forward_wave");  // the wave forms: one call per evaluation by the chain's whole wave
-  lv.grad_wave = source_defines(source, "tda_gradient_wave");
-  // the form of a source-defined prior: the term per parameter, or the wave form of a prior that couples parameters (one of them)
-  lv.prior_wave = source_defines(source, "tda_logprior_wave");
-  lv.prior_grad_wave = source_defines(source, "tda_logprior_grad");
-  if (lv.prior_wave && source_defines(source, "tda_logprior_term"))
+  lv.forms = user_forms(source);
+  if (lv.forms.both_prior_forms())
     return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines both tda_logprior_term and tda_logprior_wave (a prior has one form)");
-  int rc = compile_user_program(source, noise_kind, false, e->prior_source, e->prior_source && lv.prior_wave, lv.fwd_wave, false, m, &lv.uprog);
-  if (rc) return rc;
-  lv.uprog_prior = prior_form(e, lv);  // (a prior set later: tda_engine_init compiles again, ensure_user_programs)
+  // compiled here, so that a bad source is refused now (a prior set later: tda_engine_init compiles again, ensure_user_programs)
+  const int m_was = lv.m, noise_kind_was = lv.noise_kind;
   lv.usrc = source;
+  lv.m = m;
+  lv.noise_kind = noise_kind;
+  int rc = ensure_user_program(e, lv, false);
+  if (rc) {  // (whatever the level was set to before keeps its shape)
+    lv.m = m_was;
+    lv.noise_kind = noise_kind_was;
+    return rc;
+  }
   std::vector<double> y(data, data + m), w;
   lv.upar.release();
   if (loglike) {

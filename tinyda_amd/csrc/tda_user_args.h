@@ -3,6 +3,19 @@
 // the member order is the kernel-argument layout.
 #pragma once
 
+// The contract's signatures, each written once: the program's static_asserts and the host's refusals are built from these strings.
+#define TDA_SIG_FORWARD_WAVE "__device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)"
+#define TDA_SIG_GRADIENT_WAVE \
+  "__device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane)"
+#define TDA_SIG_GRADIENT "__device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)"
+#define TDA_SIG_LOGLIKE_TERM "__device__ double tda_loglike_term(double f, double y, double p, int o)"
+#define TDA_SIG_LOGLIKE_TERM_GRAD "__device__ double tda_loglike_term_grad(double f, double y, double p, int o)"
+#define TDA_SIG_LOGPRIOR_TERM "__device__ double tda_logprior_term(double x, double p, double q, int j)"
+#define TDA_SIG_LOGPRIOR_TERM_GRAD "__device__ double tda_logprior_term_grad(double x, double p, double q, int j)"
+#define TDA_CALL_LOGPRIOR_WAVE "tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane)"
+#define TDA_SIG_LOGPRIOR_WAVE "__device__ double " TDA_CALL_LOGPRIOR_WAVE
+#define TDA_SIG_LOGPRIOR_GRAD "__device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j)"
+
 struct UserStepArgs {
   long long N, NP;
   int d, DP, m, S, mode, prop_kind;

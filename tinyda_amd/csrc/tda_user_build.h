@@ -1,0 +1,124 @@
+// What a source-defined ("user") program is built from, without any HIP: which forms of the contract a source defines, the
+// key of one build (UserProgramSpec), its hiprtc option list and the reading of a failed compile's log.  tda_usermodel.inc is
+// the only user in the library; tests/user_build_main.cpp compiles this header alone with the host compiler.
+#pragma once
+
+#include <cctype>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "tda_user_args.h"
+#include "tinyda_amd.h"
+
+namespace {
+
+// does `source` use the identifier `name` outside // and /* */ comments, string literals and character literals?
+// (_defines in models.py is the same scan: what this function says is what is compiled)
+bool source_defines(const char* source, const char* name) {
+  const size_t n = strlen(name);
+  auto ident = [](char ch) { return isalnum((unsigned char)ch) || ch == '_'; };
+  for (const char* p = source; *p;) {
+    if (p[0] == '/' && p[1] == '/') {
+      while (*p && *p != '\n') ++p;
+    } else if (p[0] == '/' && p[1] == '*') {
+      for (p += 2; *p && !(p[0] == '*' && p[1] == '/'); ++p) {}
+      if (*p) p += 2;
+    } else if (*p == '"' || *p == '\'') {
+      const char quote = *p;
+      for (++p; *p && *p != quote; ++p)
+        if (*p == '\\' && p[1]) ++p;
+      if (*p) ++p;
+    } else if (ident(*p)) {
+      const char* q = p;
+      while (ident(*q)) ++q;
+      if ((size_t)(q - p) == n && strncmp(p, name, n) == 0) return true;
+      p = q;
+    } else {
+      ++p;
+    }
+  }
+  return false;
+}
+
+// the optional functions of the contract that a level's source defines, found once when the source is set
+struct UserForms {
+  bool forward_wave = false, gradient_wave = false;    // the wave forms of the model: one call per evaluation by the chain's whole wave
+  bool prior_term = false, prior_term_grad = false;    // a separable prior and its derivative (MALA)
+  bool prior_wave = false, prior_grad = false;         // a prior that couples parameters and its gradient (MALA)
+  bool both_prior_forms() const { return prior_term && prior_wave; }  // (a prior has one form: tda_engine_set_level_source refuses)
+};
+UserForms user_forms(const char* source) {
+  auto has = [source](const char* name) { return source_defines(source, name); };
+  return {has("tda_forward_wave"), has("tda_gradient_wave"), has("tda_logprior_term"), has("tda_logprior_term_grad"), has("tda_logprior_wave"), has("tda_logprior_grad")};
+}
+
+// what one program is compiled with: a program built with another spec than the one wanted now is built again
+struct UserProgramSpec {
+  bool mala = false;            // the MALA program (tda_user_mala_steps, tda_user_mala_grad0), not the step program
+  bool loglike_source = false;  // TDA_NOISE_SOURCE: the source's tda_loglike_term
+  int prior_form = 0;           // 0 the engine's own Gaussian / uniform code, 1 the source's tda_logprior_term, 2 its tda_logprior_wave
+  bool forward_wave = false, gradient_wave = false;  // (gradient_wave: the MALA program only, the step program calls no gradient)
+  bool operator==(const UserProgramSpec& o) const {
+    return mala == o.mala && loglike_source == o.loglike_source && prior_form == o.prior_form && forward_wave == o.forward_wave &&
+           gradient_wave == o.gradient_wave;
+  }
+};
+
+std::vector<const char*> user_program_options(const UserProgramSpec& s) {
+  std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
+  if (s.loglike_source) opts.push_back("-DTDA_LOGLIKE_SOURCE");
+  if (s.mala) opts.push_back("-DTDA_USER_MALA");
+  if (s.prior_form) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines the prior's gradient too)
+  if (s.prior_form == 2) opts.push_back("-DTDA_PRIOR_WAVE");
+  if (s.forward_wave) opts.push_back("-DTDA_FORWARD_WAVE");
+  if (s.gradient_wave) opts.push_back("-DTDA_GRADIENT_WAVE");
+  return opts;
+}
+
+// A failed compile.  A source without a function that the selected kernels call resolves to the program's tagged fallback
+// template, which a static_assert turns into a log that holds the tag: the first row below whose tag the log holds (and that
+// applies to the program) is the refusal.  Static LDS beyond the hardware's 160 KiB does not get as far as a module either: the
+// compiler's message becomes the LDS refusal.  Any other failure quotes the (truncated) compiler log.
+struct UserBuildError {
+  int code;
+  std::string message;
+};
+enum { USER_MALA = 1, USER_STEPS = 2, USER_BOTH = 3 };
+const struct UserMissingRow {
+  const char* tag;
+  int applies, code;
+  const char* message;
+} USER_MISSING[] = {
+    {"tda_forward_wave_missing", USER_BOTH, TDA_ERR_INVALID, "the source's tda_forward_wave is not " TDA_SIG_FORWARD_WAVE},
+    {"tda_gradient_wave_missing", USER_BOTH, TDA_ERR_INVALID, "the source's tda_gradient_wave is not " TDA_SIG_GRADIENT_WAVE},
+    {"tda_gradient_missing", USER_MALA, TDA_ERR_INVALID, "MALA on a source-defined model: the source defines no " TDA_SIG_GRADIENT},
+    {"tda_loglike_term_grad_missing", USER_MALA, TDA_ERR_INVALID, "MALA with a source-defined likelihood: the source defines no " TDA_SIG_LOGLIKE_TERM_GRAD},
+    {"tda_loglike_term_missing", USER_STEPS, TDA_ERR_INVALID, "a source-defined likelihood: the source defines no " TDA_SIG_LOGLIKE_TERM},
+    {"tda_logprior_wave_missing", USER_BOTH, TDA_ERR_INVALID, "a source-defined prior: the source's tda_logprior_wave is not " TDA_SIG_LOGPRIOR_WAVE},
+    {"tda_logprior_grad_missing", USER_MALA, TDA_ERR_INVALID, "a source-defined prior under MALA: the source defines no " TDA_SIG_LOGPRIOR_GRAD},
+    {"tda_logprior_term_grad_missing", USER_MALA, TDA_ERR_INVALID, "a source-defined prior under MALA: the source defines no " TDA_SIG_LOGPRIOR_TERM_GRAD},
+    {"tda_logprior_term_missing", USER_BOTH, TDA_ERR_INVALID,
+     "a source-defined prior: the source defines no " TDA_SIG_LOGPRIOR_TERM " (or, for a prior that couples parameters, " TDA_CALL_LOGPRIOR_WAVE ")"},
+};
+UserBuildError diagnose_user_build(std::string log, const UserProgramSpec& spec, int m) {
+  char buf[512];  // (the length of the engine's error text)
+  unsigned long lds_need = 0, lds_limit = 0;
+  const size_t at = log.find("local memory (");
+  if (at != std::string::npos && sscanf(log.c_str() + at, "local memory (%lu) exceeds limit (%lu)", &lds_need, &lds_limit) == 2) {
+    snprintf(buf, sizeof buf,
+             "a source-defined model holds at most 64 KiB of LDS per chain: this source declares %lu bytes (parameters, gradient, "
+             "TDA_WORKSPACE and its own __shared__ arrays), more than the %lu bytes of the hardware, before the %zu bytes "
+             "for its %d outputs",
+             lds_need, lds_limit, (size_t)m * sizeof(double), m);
+    return {TDA_ERR_UNSUPPORTED, buf};
+  }
+  for (const UserMissingRow& row : USER_MISSING)
+    if ((row.applies & (spec.mala ? USER_MALA : USER_STEPS)) && log.find(row.tag) != std::string::npos) return {row.code, row.message};
+  if (log.size() > 400) log.resize(400);
+  snprintf(buf, sizeof buf, "the forward-model source does not compile%s: %s", spec.mala ? " with the MALA kernels" : "", log.c_str());
+  return {TDA_ERR_INVALID, buf};
+}
+
+}  // namespace

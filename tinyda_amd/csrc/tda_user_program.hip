@@ -1,125 +1,100 @@
 // The programs that hiprtc compiles at run time together with a user's HIP source (tda_usermodel.inc; embedded in the library as
-// text, and compiled offline as it stands by tests/test_loglike_source.py).  The user's source is the header "tda_user_source.h":
+// text, and compiled offline as it stands by tests/extprogram.py).  The user's source is the header "tda_user_source.h":
 //     __device__ double tda_forward(const double* theta, int dim, int o);     // output o of F(theta)
 // so that non-linear models run fused on the device instead of through the host protocol (the reference evaluates a Python
 // callable per chain and step, posterior.py:95-96).  One wave per chain: lane j owns parameter j (and j + 64 at 65 .. 128
 // parameters), the lanes stride over the outputs.  Same step semantics, records and RNG inputs as k_mh_steps; proposals,
 // adaptation and Cholesky stay the engine's own kernels.
 // A model whose outputs all come from one solve (an integrator, a time-stepping scheme, a tridiagonal solve) defines the
-// wave-cooperative form instead: the 64 lanes of the chain's wave call it together, once per evaluation,
-//     __device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane);
+// wave-cooperative form instead, tda_forward_wave: the 64 lanes of the chain's wave call it together, once per evaluation;
 // theta and out are LDS (out: n_outputs doubles, NaN before the call: an entry left unwritten rejects the proposal), `work` is
 // TDA_WORKSPACE doubles of LDS of the chain's own (a #define of the source; 0 / undefined: null), __syncthreads() inside is legal
 // and a wave barrier (one wave per workgroup).
-// Six compile options select what is built (the file itself never defines them):
+// Six compile options select what is built (the file itself never defines them; the signature of every function named here is
+// written once, TDA_SIG_* in tda_user_args.h):
 //   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
 //                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
-//     __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j);
-//                         = (J(theta)^T sensitivity)_j (the reference's model.gradient(parameters, sensitivity), proposal.py:996-998)
+//                         tda_gradient = (J(theta)^T sensitivity)_j (the reference's model.gradient(parameters, sensitivity), proposal.py:996-998)
 //   -DTDA_LOGLIKE_SOURCE  source-defined likelihood (TDA_NOISE_SOURCE): log L(F) = sum_o tda_loglike_term(F_o, y_o, p_o, o), defined
 //                         by the source after tda_forward; the args' `w` then carries p (not inverted).  MALA also needs
 //                         tda_loglike_term_grad, d term / d f.  The Gaussian kinds compile without it.
 //   -DTDA_PRIOR_SOURCE    source-defined prior (tda_engine_set_prior_joint, kind TDA_PRIOR_SOURCE): log p(theta) = sum_j
 //                         tda_logprior_term(theta_j, p_j, q_j, j), defined by the source; the args' `pr_mean` / `pr_pinv` then carry
 //                         p / q as given.  tda_user_steps and the MALA kernels evaluate it (the level action carries the log-prior
-//                         of the state it promotes).  MALA also needs tda_logprior_term_grad, d term / d x:
-//     __device__ double tda_logprior_term_grad(double x, double p, double q, int j);
+//                         of the state it promotes).  MALA also needs tda_logprior_term_grad, d term / d x.
 //                         Outside the support its value is free (NaN, +-inf, anything): the term is -inf there and rejects.
 //   -DTDA_PRIOR_WAVE      (in addition to -DTDA_PRIOR_SOURCE) the prior couples parameters: the source defines the wave form instead of
-//                         the term.  The chain's 64 lanes call it together, once per evaluation, and the engine sums the 64 returns:
-//     __device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane);
-//                         theta is the proposal in LDS (entries at index >= dim are unspecified), p / q the arrays as given (device
+//                         the term, tda_logprior_wave.  The chain's 64 lanes call it together, once per evaluation, and the engine sums
+//                         the 64 returns.  theta is the proposal in LDS (entries at index >= dim are unspecified), p / q the arrays as given (device
 //                         memory).  Every lane is called, lanes >= dim too; how the terms spread over the lanes is the function's own
 //                         business (for (j = lane; j < dim; j += 64)).  Pure: no barriers, no workspace, no writes.  A NaN or -inf
-//                         share rejects.  MALA also needs d log p / d theta_j, called by the lane that owns parameter j:
-//     __device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j);
+//                         share rejects.  MALA also needs tda_logprior_grad, d log p / d theta_j, called by the lane that owns parameter j.
 //   -DTDA_FORWARD_WAVE    the source defines tda_forward_wave: the outputs are taken from LDS (s_out[m], dynamic; the MALA program
 //                         lets the model write into its s_sens[m]) after one call, not from tda_forward(theta, dim, o) per output
-//   -DTDA_GRADIENT_WAVE   (MALA program) the source defines the vector-Jacobian product in the same form, one call for all parameters,
-//     __device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane);
-//                         grad: LDS, 128 doubles, zero before the call; `work` is what tda_forward_wave left at the same theta
+//   -DTDA_GRADIENT_WAVE   (MALA program) the source defines the vector-Jacobian product in the same form, tda_gradient_wave, one call for all
+//                         parameters.  grad: LDS, 128 doubles, zero before the call; `work` is what tda_forward_wave left at the same theta
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
 
-// Fallbacks a call resolves to when the source does not define a function of the contract's signature (a non-template function of
-// that signature wins overload resolution against them); the static_asserts below turn them into a message, not an unresolved
-// symbol at load.
+// TDA_FALLBACK: what a call resolves to when the source does not define a function of the contract's signature (a non-template
+// function of that signature wins overload resolution against it).  TDA_REQUIRE, after the source: a call that still resolves to
+// the fallback becomes a message that holds the tag <name>_missing and the signature, not an unresolved symbol at load.
+#define TDA_FALLBACK(name, ...) \
+  struct name##_missing {};     \
+  template <class T>            \
+  __device__ name##_missing name(__VA_ARGS__) { return {}; }
+#define TDA_REQUIRE(name, message, ...) static_assert(!__is_same(decltype(name(__VA_ARGS__)), name##_missing), #name "_missing: " message)
 #ifdef TDA_FORWARD_WAVE
-struct tda_forward_wave_missing {};
-template <class L>
-__device__ tda_forward_wave_missing tda_forward_wave(const double*, int, double*, int, double*, L) { return {}; }
+TDA_FALLBACK(tda_forward_wave, const double*, int, double*, int, double*, T)
 #endif
 #if defined(TDA_USER_MALA) && defined(TDA_GRADIENT_WAVE)
-struct tda_gradient_wave_missing {};
-template <class L>
-__device__ tda_gradient_wave_missing tda_gradient_wave(const double*, int, const double*, int, double*, double*, L) { return {}; }
+TDA_FALLBACK(tda_gradient_wave, const double*, int, const double*, int, double*, double*, T)
 #elif defined(TDA_USER_MALA)
-struct tda_gradient_missing {};
-template <class J>
-__device__ tda_gradient_missing tda_gradient(const double*, int, const double*, int, J) { return {}; }
+TDA_FALLBACK(tda_gradient, const double*, int, const double*, int, T)
 #endif
 #ifdef TDA_LOGLIKE_SOURCE
-struct tda_loglike_term_missing {};
-template <class O>
-__device__ tda_loglike_term_missing tda_loglike_term(double, double, double, O) { return {}; }
-struct tda_loglike_term_grad_missing {};
-template <class O>
-__device__ tda_loglike_term_grad_missing tda_loglike_term_grad(double, double, double, O) { return {}; }
+TDA_FALLBACK(tda_loglike_term, double, double, double, T)
+TDA_FALLBACK(tda_loglike_term_grad, double, double, double, T)
 #endif
 #ifdef TDA_PRIOR_SOURCE
-struct tda_logprior_term_missing {};
-template <class J>
-__device__ tda_logprior_term_missing tda_logprior_term(double, double, double, J) { return {}; }
-struct tda_logprior_term_grad_missing {};
-template <class J>
-__device__ tda_logprior_term_grad_missing tda_logprior_term_grad(double, double, double, J) { return {}; }
+TDA_FALLBACK(tda_logprior_term, double, double, double, T)
+TDA_FALLBACK(tda_logprior_term_grad, double, double, double, T)
 #endif
 #if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
-struct tda_logprior_wave_missing {};
-template <class L>
-__device__ tda_logprior_wave_missing tda_logprior_wave(const double*, int, const double*, const double*, L) { return {}; }
-struct tda_logprior_grad_missing {};
-template <class J>
-__device__ tda_logprior_grad_missing tda_logprior_grad(const double*, int, const double*, const double*, J) { return {}; }
+TDA_FALLBACK(tda_logprior_wave, const double*, int, const double*, const double*, T)
+TDA_FALLBACK(tda_logprior_grad, const double*, int, const double*, const double*, T)
 #endif
 
 #include "tda_user_source.h"
 
+#define TDA_CD (const double*)nullptr
+#define TDA_D (double*)nullptr
 #ifdef TDA_FORWARD_WAVE
-static_assert(!__is_same(decltype(tda_forward_wave((const double*)nullptr, 0, (double*)nullptr, 0, (double*)nullptr, 0)), tda_forward_wave_missing),
-              "tda_forward_wave_missing: the wave form of the model is __device__ void tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)");
+TDA_REQUIRE(tda_forward_wave, "the wave form of the model is " TDA_SIG_FORWARD_WAVE, TDA_CD, 0, TDA_D, 0, TDA_D, 0);
 #endif
 #if defined(TDA_USER_MALA) && defined(TDA_GRADIENT_WAVE)
-static_assert(!__is_same(decltype(tda_gradient_wave((const double*)nullptr, 0, (const double*)nullptr, 0, (double*)nullptr, (double*)nullptr, 0)), tda_gradient_wave_missing),
-              "tda_gradient_wave_missing: the wave form of the gradient is __device__ void tda_gradient_wave(const double* theta, int dim, const double* sensitivity, int n_outputs, double* grad, double* work, int lane)");
+TDA_REQUIRE(tda_gradient_wave, "the wave form of the gradient is " TDA_SIG_GRADIENT_WAVE, TDA_CD, 0, TDA_CD, 0, TDA_D, TDA_D, 0);
 #elif defined(TDA_USER_MALA)
-static_assert(!__is_same(decltype(tda_gradient((const double*)nullptr, 0, (const double*)nullptr, 0, 0)), tda_gradient_missing),
-              "tda_gradient_missing: MALA needs __device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)");
+TDA_REQUIRE(tda_gradient, "MALA needs " TDA_SIG_GRADIENT, TDA_CD, 0, TDA_CD, 0, 0);
 #endif
 #ifdef TDA_LOGLIKE_SOURCE
-static_assert(!__is_same(decltype(tda_loglike_term(0.0, 0.0, 0.0, 0)), tda_loglike_term_missing),
-              "tda_loglike_term_missing: a source-defined likelihood needs __device__ double tda_loglike_term(double f, double y, double p, int o)");
+TDA_REQUIRE(tda_loglike_term, "a source-defined likelihood needs " TDA_SIG_LOGLIKE_TERM, 0.0, 0.0, 0.0, 0);
 #ifdef TDA_USER_MALA
-static_assert(!__is_same(decltype(tda_loglike_term_grad(0.0, 0.0, 0.0, 0)), tda_loglike_term_grad_missing),
-              "tda_loglike_term_grad_missing: MALA needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o)");
+TDA_REQUIRE(tda_loglike_term_grad, "MALA needs " TDA_SIG_LOGLIKE_TERM_GRAD, 0.0, 0.0, 0.0, 0);
 #endif
 #endif
 #if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
-static_assert(!__is_same(decltype(tda_logprior_wave((const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, 0)), tda_logprior_wave_missing),
-              "tda_logprior_wave_missing: the wave form of the prior is __device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane)");
+TDA_REQUIRE(tda_logprior_wave, "the wave form of the prior is " TDA_SIG_LOGPRIOR_WAVE, TDA_CD, 0, TDA_CD, TDA_CD, 0);
 #ifdef TDA_USER_MALA
-static_assert(!__is_same(decltype(tda_logprior_grad((const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, 0)), tda_logprior_grad_missing),
-              "tda_logprior_grad_missing: MALA under TDA_PRIOR_WAVE needs __device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j)");
+TDA_REQUIRE(tda_logprior_grad, "MALA under TDA_PRIOR_WAVE needs " TDA_SIG_LOGPRIOR_GRAD, TDA_CD, 0, TDA_CD, TDA_CD, 0);
 #endif
 #endif
 #ifdef TDA_PRIOR_SOURCE
 #if !defined(TDA_PRIOR_WAVE)  // (the wave form stands in for the term and its derivative)
-static_assert(!__is_same(decltype(tda_logprior_term(0.0, 0.0, 0.0, 0)), tda_logprior_term_missing),
-              "tda_logprior_term_missing: a source-defined prior needs __device__ double tda_logprior_term(double x, double p, double q, int j)");
+TDA_REQUIRE(tda_logprior_term, "a source-defined prior needs " TDA_SIG_LOGPRIOR_TERM, 0.0, 0.0, 0.0, 0);
 #ifdef TDA_USER_MALA
-static_assert(!__is_same(decltype(tda_logprior_term_grad(0.0, 0.0, 0.0, 0)), tda_logprior_term_grad_missing),
-              "tda_logprior_term_grad_missing: MALA under TDA_PRIOR_SOURCE needs __device__ double tda_logprior_term_grad(double x, double p, double q, int j)");
+TDA_REQUIRE(tda_logprior_term_grad, "MALA under TDA_PRIOR_SOURCE needs " TDA_SIG_LOGPRIOR_TERM_GRAD, 0.0, 0.0, 0.0, 0);
 #endif
 #endif
 #endif

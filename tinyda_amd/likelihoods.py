@@ -8,12 +8,11 @@ covariance with equal entries becomes isotropic, a diagonal one diagonal, anythi
 through it with the term library `csrc/tda_prior_families.h`.
 """
 import os
-import re
 
 import numpy as np
 
 from . import _lib
-from .models import _strip_comments
+from .models import _defines
 
 
 def _check_covariance(data, covariance):
@@ -141,10 +140,9 @@ class DeviceLogLike:
                            else np.atleast_1d(np.asarray(parameters, dtype=np.float64)))
         if self.data.ndim != 1 or self.parameters.shape != self.data.shape:
             raise ValueError("data and parameters must be vectors with one entry per model output")
-        stripped = _strip_comments(self.source)
-        if not re.search(r"\btda_loglike_term\s*\(", stripped):
+        if not _defines(self.source, "tda_loglike_term"):
             raise ValueError("the source must define __device__ double tda_loglike_term(double f, double y, double p, int o)")
-        self.has_gradient = re.search(r"\btda_loglike_term_grad\s*\(", stripped) is not None
+        self.has_gradient = _defines(self.source, "tda_loglike_term_grad")
         self.reference = reference
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:
@@ -217,17 +215,15 @@ class DevicePrior:
             raise ValueError("p and q must be vectors with one entry per parameter")
         if not (np.all(np.isfinite(self.p)) and np.all(np.isfinite(self.q))):
             raise ValueError("p and q must be finite")
-        stripped = _strip_comments(self.source)
-        term = re.search(r"\btda_logprior_term\s*\(", stripped) is not None
-        self.coupled = re.search(r"\btda_logprior_wave\s*\(", stripped) is not None
+        term = _defines(self.source, "tda_logprior_term")
+        self.coupled = _defines(self.source, "tda_logprior_wave")
         if term and self.coupled:
             raise ValueError("the source defines both tda_logprior_term and tda_logprior_wave: a prior has one form")
         if not term and not self.coupled:
             raise ValueError("the source must define __device__ double tda_logprior_term(double x, double p, double q, int j) (or, for a "
                              "prior that couples parameters, __device__ double tda_logprior_wave(const double* theta, int dim, "
                              "const double* p, const double* q, int lane))")
-        grad = r"\btda_logprior_grad\s*\(" if self.coupled else r"\btda_logprior_term_grad\s*\("
-        self.has_gradient = re.search(grad, stripped) is not None
+        self.has_gradient = _defines(self.source, "tda_logprior_grad" if self.coupled else "tda_logprior_term_grad")
         self.reference = reference
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:

@@ -78,13 +78,12 @@ class DeviceModel:
         self.source = str(source)
         self.n_outputs = int(n_outputs)
         self.reference = reference
-        code = _code_only(self.source)
-        self.has_forward_wave = re.search(r"\btda_forward_wave\b", code) is not None
-        self.has_gradient_wave = re.search(r"\btda_gradient_wave\b", code) is not None
-        if not (self.has_forward_wave or re.search(r"\btda_forward\b", code)):
+        self.has_forward_wave = _defines(self.source, "tda_forward_wave")
+        self.has_gradient_wave = _defines(self.source, "tda_gradient_wave")
+        if not (self.has_forward_wave or _defines(self.source, "tda_forward")):
             raise ValueError("the source must define __device__ double tda_forward(const double* theta, int dim, int o) or __device__ void "
                              "tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)")
-        self.has_gradient = self.has_gradient_wave or re.search(r"\btda_gradient\b", code) is not None
+        self.has_gradient = self.has_gradient_wave or _defines(self.source, "tda_gradient")
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:
             self.gradient = self._reference_gradient  # (an attribute only then: MALA.setup_proposal looks for it)
@@ -99,16 +98,14 @@ class DeviceModel:
         return np.atleast_1d(np.asarray(self.reference(np.asarray(parameters, dtype=np.float64)), dtype=np.float64))
 
 
-def _code_only(source):
-    """HIP source without its // and /* */ comments, string literals and character literals: what the engine searches for the
-    identifiers of the wave forms (source_defines in csrc/tda_usermodel.inc skips the same; the engine's answer is what is
-    compiled, the attributes of DeviceModel only report it)."""
-    return re.sub(r"""//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\])*"|'(?:\\.|[^'\\])*'""", " ", source, flags=re.S)
+_TOKEN = re.compile(r"""//[^\n]*|/\*.*?(?:\*/|\Z)|"(?:\\.?|[^"\\])*(?:"|\Z)|'(?:\\.?|[^'\\])*(?:'|\Z)|([A-Za-z0-9_]+)""", re.S)
 
 
-def _strip_comments(source):
-    """HIP source without its // and /* */ comments (string literals are left alone)."""
-    return re.sub(r'//[^\n]*|/\*.*?\*/|("(?:\\.|[^"\\])*")', lambda mt: mt.group(1) or " ", source, flags=re.S)
+def _defines(source, name):
+    """Does the HIP source use the identifier `name` outside // and /* */ comments, string literals and character literals?  The
+    engine's own rule (source_defines in csrc/tda_user_build.h, token for token: an unterminated comment or literal runs to the end
+    of the text), so that what DeviceModel, DeviceLogLike and DevicePrior report is what the engine compiles."""
+    return any(mt.group(1) == name for mt in _TOKEN.finditer(source))
 
 
 class BatchedModel:
