@@ -437,7 +437,30 @@ int tda_engine_set_prior_joint(tda_engine* e, const int32_t* kind, const double*
  * tda_gradient (the sensitivity is then d term / d f).  A source without tda_loglike_term (MALA: without
  * tda_loglike_term_grad, at tda_engine_init) returns TDA_ERR_INVALID naming the signature.  tda_engine_init refuses it with
  * TDA_ERR_UNSUPPORTED under DREAM(Z), Independence, operator-weighted pCN, an error model and randomised subchain lengths;
- * tda_engine_set_level / _callback refuse the kind.  Likelihoods that couple outputs are not covered.
+ * tda_engine_set_level / _callback refuse the kind.
+ * Likelihoods that couple outputs (correlated noise such as AR(1) residuals, a noise level integrated out, multinomial / softmax
+ * counts, constraints between neighbouring outputs): the source defines the wave form INSTEAD of tda_loglike_term (the engine looks
+ * for the identifiers in the comment-stripped source; a source that defines both forms returns TDA_ERR_INVALID from
+ * tda_engine_set_level_source).  The noise kind stays TDA_NOISE_SOURCE.
+ *     __device__ double tda_loglike_wave(const double* f, int n_outputs, const double* y, const double* p, int lane);
+ * The chain's 64 lanes call it together, once per evaluation, and the engine sums the 64 return values.  f holds the model's
+ * outputs in LDS, complete before the call; y and p are data and noise in device memory, as given.  Every lane is called, lanes
+ * >= n_outputs included, and the call site is converged; how the work spreads over the lanes is the function's own business, the
+ * idiom is for (o = lane; o < n_outputs; o += 64).  No barriers, no workspace, no writes.  Wave shuffles are legal: a likelihood
+ * that is a non-linear function of a reduction reduces with __shfl_xor and returns the value from one lane, 0 from the others --
+ * the noise level integrated out, log L = -(a + m / 2) log(b + 1/2 sum_o r_o^2) with a = 2, b = 1.5:
+ *     double s = 0.0;
+ *     for (int o = lane; o < n_outputs; o += 64) { const double r = (f[o] - y[o]) / p[o]; s += r * r; }
+ *     for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+ *     return lane == 0 ? -(2.0 + 0.5 * n_outputs) * log(1.5 + 0.5 * s) : 0.0;
+ * A NaN or -inf share rejects the proposal.  Everything above applies unchanged: where it is lowered, every refusal.  MALA needs
+ *     __device__ void tda_loglike_grad_wave(const double* f, int n_outputs, const double* y, const double* p, double* sens, int lane);
+ * one call by the whole wave that writes d log L / d f_o for every output into sens (n_outputs doubles of LDS, NaN before the
+ * call, a barrier after it: an entry left unwritten makes the gradient NaN, which rejects the proposal); without it
+ * tda_engine_init returns TDA_ERR_INVALID naming the signature, as a tda_loglike_wave of another signature does from
+ * tda_engine_set_level_source.  LDS per chain: 8 (n_outputs + 128 + TDA_WORKSPACE) bytes in the step program, and
+ * 8 (2 n_outputs + 128 + TDA_WORKSPACE) (+ 1 KiB with tda_gradient_wave) in the MALA program, which keeps the outputs behind the
+ * sensitivities; beyond 64 KiB the level is refused with TDA_ERR_UNSUPPORTED and both byte counts.
  * Wave-cooperative models (one solve gives all outputs: an integrator, a time-stepping scheme, a tridiagonal solve): instead of
  * tda_forward the source may define (the engine looks for the identifiers in the comment-stripped source; with both, this one is used)
  *     #define TDA_WORKSPACE 3072   // optional: doubles of LDS scratch of the chain's own, handed over as `work` (default 0: null)

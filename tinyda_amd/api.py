@@ -64,6 +64,9 @@ def _loglike_source_refusal(low, n_levels, proposal, error_model, randomize):
         pc = np.asarray(low["prior_cov"])
         if n_levels != 1 or ("prior_joint" in low and "prior_source" not in low) or np.count_nonzero(pc - np.diag(np.diag(pc))):
             return "MALA with a DeviceLogLike: single level, multivariate normal prior with diagonal covariance or a DevicePrior with its gradient"
+        if low.get("loglike_coupled") and not low["loglike_has_gradient"]:
+            return ("MALA with a DeviceLogLike that couples outputs needs __device__ void tda_loglike_grad_wave(const double* f, int n_outputs, "
+                    "const double* y, const double* p, double* sens, int lane) in the likelihood source")
         if not low["loglike_has_gradient"]:
             return ("MALA with a DeviceLogLike needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o) "
                     "in the likelihood source")
@@ -101,6 +104,9 @@ def _prior_source_refusal(low, n_levels, proposal, error_model, randomize):
                     "int n_outputs, int j) (or tda_gradient_wave) in the model source" % who)
         if np.asarray(low["data"]).shape[0] > 2048:
             return "%s under MALA over a source-defined model: at most 2048 outputs" % who
+        if low["noise_kind"] == _lib.NOISE_SOURCE and low.get("loglike_coupled") and not low.get("loglike_has_gradient"):
+            return ("%s under MALA with a DeviceLogLike that couples outputs needs __device__ void tda_loglike_grad_wave(const double* f, "
+                    "int n_outputs, const double* y, const double* p, double* sens, int lane) in the likelihood source" % who)
         if low["noise_kind"] == _lib.NOISE_SOURCE and not low.get("loglike_has_gradient"):
             return ("%s under MALA with a DeviceLogLike needs __device__ double tda_loglike_term_grad(double f, double y, double p, int o) "
                     "in the likelihood source" % who)

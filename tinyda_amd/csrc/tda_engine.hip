@@ -1112,11 +1112,12 @@ int ext_step(tda_engine* e, const Level& lv, const ExtArgs& xa) {
   return TDA_OK;
 }
 
-// what a level's program is to be compiled with now (the prior's form: UserProgramSpec::prior_form)
+// what a level's program is to be compiled with now (the prior's form: UserProgramSpec::prior_form; the likelihood's: loglike_wave)
 UserProgramSpec user_program_spec(const tda_engine* e, const Level& lv, bool mala) {
   UserProgramSpec s;
   s.mala = mala;
   s.loglike_source = lv.noise_kind == TDA_NOISE_SOURCE;
+  s.loglike_wave = s.loglike_source && lv.forms.loglike_wave;
   s.prior_form = !e->prior_source ? 0 : lv.forms.prior_wave ? 2 : 1;
   s.forward_wave = lv.forms.forward_wave;
   s.gradient_wave = mala && lv.forms.gradient_wave;

@@ -439,7 +439,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   if (user_mala) {
     UserMalaArgs ga{};
     if ((rc = fill_user_mala_args(e, e->levels[0], ga))) return rc;
-    if ((rc = launch_user(e->levels[0].uprog_mala.grad0, ga, user_mala_lds(ga), e->stream))) return rc;
+    if ((rc = launch_user(e->levels[0].uprog_mala.grad0, ga, user_mala_lds(e->levels[0].uprog_mala.spec, ga.m), e->stream))) return rc;
   } else if (mala) {
     const int64_t nt = NP * DP;
     hipLaunchKernelGGL(k_mala_grad0, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, e->stream, NP, DP, e->mala_H.p, e->mala_c.p,

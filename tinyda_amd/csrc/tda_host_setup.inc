@@ -317,16 +317,20 @@ int tda_engine_set_level_source(tda_engine* e, int level, const char* source, in
   if (!e || !source || !data || !noise) return fail(TDA_ERR_INVALID, "null argument");
   if (level < 0 || level >= (int)e->levels.size()) return fail(TDA_ERR_INVALID, "level %d out of range", level);
   if (m < 1) return fail(TDA_ERR_INVALID, "m must be >= 1");
-  const bool loglike = noise_kind == TDA_NOISE_SOURCE;  // the likelihood is part of the source (tda_loglike_term), `noise` its parameters
+  const bool loglike = noise_kind == TDA_NOISE_SOURCE;  // the likelihood is part of the source (tda_loglike_term, or tda_loglike_wave for one that couples outputs), `noise` its parameters
   if (!loglike && noise_kind != TDA_NOISE_ISO && noise_kind != TDA_NOISE_DIAG && noise_kind != TDA_NOISE_DENSE && !(noise_kind == TDA_NOISE_ADAPTIVE && e->nlev > 1))
     return fail(TDA_ERR_UNSUPPORTED, "noise kind %d (AdaptiveGaussianLogLike only below the finest level of a hierarchy)", noise_kind);
   HIP_TRY(hipSetDevice(e->cfg.device));
   Level& lv = e->levels[level];
+  // (a source refused here leaves the level as it was: its text, its forms and its programs belong together)
+  const UserForms forms = user_forms(source);
+  if (forms.both_prior_forms())
+    return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines both tda_logprior_term and tda_logprior_wave (a prior has one form)");
+  if (forms.both_loglike_forms())
+    return fail(TDA_ERR_INVALID, "a source-defined likelihood: the source defines both tda_loglike_term and tda_loglike_wave (a likelihood has one form)");
   lv.uprog.unload();
   lv.uprog_mala.unload();
-  lv.forms = user_forms(source);
-  if (lv.forms.both_prior_forms())
-    return fail(TDA_ERR_INVALID, "a source-defined prior: the source defines both tda_logprior_term and tda_logprior_wave (a prior has one form)");
+  lv.forms = forms;
   // compiled here, so that a bad source is refused now (a prior set later: tda_engine_init compiles again, ensure_user_programs)
   const int m_was = lv.m, noise_kind_was = lv.noise_kind;
   lv.usrc = source;

@@ -365,7 +365,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       ga.rec_stats = sa.rec_stats;
       ga.rec_acc = sa.rec_acc;
       ScopedTimer tm(e, 1);
-      if ((urc = launch_user(lv.uprog_mala.steps, ga, user_mala_lds(ga), e->stream))) return urc;
+      if ((urc = launch_user(lv.uprog_mala.steps, ga, user_mala_lds(lv.uprog_mala.spec, ga.m), e->stream))) return urc;
     } else if (lv.model == MODEL_USER) {
       UserStepArgs ua{};
       int urc = fill_user_args(e, lv, ua);

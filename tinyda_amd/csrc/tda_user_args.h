@@ -10,6 +10,9 @@
 #define TDA_SIG_GRADIENT "__device__ double tda_gradient(const double* theta, int dim, const double* sensitivity, int n_outputs, int j)"
 #define TDA_SIG_LOGLIKE_TERM "__device__ double tda_loglike_term(double f, double y, double p, int o)"
 #define TDA_SIG_LOGLIKE_TERM_GRAD "__device__ double tda_loglike_term_grad(double f, double y, double p, int o)"
+#define TDA_SIG_LOGLIKE_WAVE "__device__ double tda_loglike_wave(const double* f, int n_outputs, const double* y, const double* p, int lane)"
+#define TDA_SIG_LOGLIKE_GRAD_WAVE \
+  "__device__ void tda_loglike_grad_wave(const double* f, int n_outputs, const double* y, const double* p, double* sens, int lane)"
 #define TDA_SIG_LOGPRIOR_TERM "__device__ double tda_logprior_term(double x, double p, double q, int j)"
 #define TDA_SIG_LOGPRIOR_TERM_GRAD "__device__ double tda_logprior_term_grad(double x, double p, double q, int j)"
 #define TDA_CALL_LOGPRIOR_WAVE "tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane)"

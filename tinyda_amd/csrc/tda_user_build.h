@@ -47,28 +47,43 @@ struct UserForms {
   bool forward_wave = false, gradient_wave = false;    // the wave forms of the model: one call per evaluation by the chain's whole wave
   bool prior_term = false, prior_term_grad = false;    // a separable prior and its derivative (MALA)
   bool prior_wave = false, prior_grad = false;         // a prior that couples parameters and its gradient (MALA)
+  bool loglike_term = false, loglike_wave = false, loglike_grad_wave = false;  // a separable likelihood, one that couples outputs, and its gradient (MALA)
   bool both_prior_forms() const { return prior_term && prior_wave; }  // (a prior has one form: tda_engine_set_level_source refuses)
+  bool both_loglike_forms() const { return loglike_term && loglike_wave; }  // (and so has a likelihood)
 };
 UserForms user_forms(const char* source) {
   auto has = [source](const char* name) { return source_defines(source, name); };
-  return {has("tda_forward_wave"), has("tda_gradient_wave"), has("tda_logprior_term"), has("tda_logprior_term_grad"), has("tda_logprior_wave"), has("tda_logprior_grad")};
+  return {has("tda_forward_wave"), has("tda_gradient_wave"), has("tda_logprior_term"), has("tda_logprior_term_grad"), has("tda_logprior_wave"), has("tda_logprior_grad"),
+          has("tda_loglike_term"), has("tda_loglike_wave"), has("tda_loglike_grad_wave")};
 }
 
 // what one program is compiled with: a program built with another spec than the one wanted now is built again
 struct UserProgramSpec {
   bool mala = false;            // the MALA program (tda_user_mala_steps, tda_user_mala_grad0), not the step program
-  bool loglike_source = false;  // TDA_NOISE_SOURCE: the source's tda_loglike_term
+  bool loglike_source = false;  // TDA_NOISE_SOURCE: the source's tda_loglike_term (or its tda_loglike_wave: loglike_wave below)
   int prior_form = 0;           // 0 the engine's own Gaussian / uniform code, 1 the source's tda_logprior_term, 2 its tda_logprior_wave
   bool forward_wave = false, gradient_wave = false;  // (gradient_wave: the MALA program only, the step program calls no gradient)
+  bool loglike_wave = false;    // (with loglike_source) the source's tda_loglike_wave, not its tda_loglike_term
   bool operator==(const UserProgramSpec& o) const {
     return mala == o.mala && loglike_source == o.loglike_source && prior_form == o.prior_form && forward_wave == o.forward_wave &&
-           gradient_wave == o.gradient_wave;
+           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave;
   }
 };
+
+// dynamic LDS of the MALA kernels: the sensitivity of the m outputs (s_sens[m] of tda_user_program.hip), and behind it the
+// outputs themselves under a likelihood that couples them
+inline size_t user_mala_lds(const UserProgramSpec& spec, int m) { return (spec.loglike_source && spec.loglike_wave ? 2 : 1) * (size_t)m * sizeof(double); }
+// dynamic LDS of a program's kernels for m outputs: the MALA program's buffer, or the step program's s_out[m] under a wave form of
+// the model or of the likelihood (0 without one)
+inline size_t user_dynamic_lds(const UserProgramSpec& spec, int m) {
+  if (spec.mala) return user_mala_lds(spec, m);
+  return spec.forward_wave || (spec.loglike_source && spec.loglike_wave) ? (size_t)m * sizeof(double) : 0;
+}
 
 std::vector<const char*> user_program_options(const UserProgramSpec& s) {
   std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   if (s.loglike_source) opts.push_back("-DTDA_LOGLIKE_SOURCE");
+  if (s.loglike_source && s.loglike_wave) opts.push_back("-DTDA_LOGLIKE_WAVE");  // (under MALA: tda_loglike_grad_wave too)
   if (s.mala) opts.push_back("-DTDA_USER_MALA");
   if (s.prior_form) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines the prior's gradient too)
   if (s.prior_form == 2) opts.push_back("-DTDA_PRIOR_WAVE");
@@ -94,6 +109,9 @@ const struct UserMissingRow {
     {"tda_forward_wave_missing", USER_BOTH, TDA_ERR_INVALID, "the source's tda_forward_wave is not " TDA_SIG_FORWARD_WAVE},
     {"tda_gradient_wave_missing", USER_BOTH, TDA_ERR_INVALID, "the source's tda_gradient_wave is not " TDA_SIG_GRADIENT_WAVE},
     {"tda_gradient_missing", USER_MALA, TDA_ERR_INVALID, "MALA on a source-defined model: the source defines no " TDA_SIG_GRADIENT},
+    {"tda_loglike_wave_missing", USER_BOTH, TDA_ERR_INVALID, "a source-defined likelihood: the source's tda_loglike_wave is not " TDA_SIG_LOGLIKE_WAVE},
+    {"tda_loglike_grad_wave_missing", USER_MALA, TDA_ERR_INVALID,
+     "MALA with a source-defined likelihood that couples outputs: the source defines no " TDA_SIG_LOGLIKE_GRAD_WAVE},
     {"tda_loglike_term_grad_missing", USER_MALA, TDA_ERR_INVALID, "MALA with a source-defined likelihood: the source defines no " TDA_SIG_LOGLIKE_TERM_GRAD},
     {"tda_loglike_term_missing", USER_STEPS, TDA_ERR_INVALID, "a source-defined likelihood: the source defines no " TDA_SIG_LOGLIKE_TERM},
     {"tda_logprior_wave_missing", USER_BOTH, TDA_ERR_INVALID, "a source-defined prior: the source's tda_logprior_wave is not " TDA_SIG_LOGPRIOR_WAVE},
@@ -110,8 +128,9 @@ UserBuildError diagnose_user_build(std::string log, const UserProgramSpec& spec,
     snprintf(buf, sizeof buf,
              "a source-defined model holds at most 64 KiB of LDS per chain: this source declares %lu bytes (parameters, gradient, "
              "TDA_WORKSPACE and its own __shared__ arrays), more than the %lu bytes of the hardware, before the %zu bytes "
-             "for its %d outputs",
-             lds_need, lds_limit, (size_t)m * sizeof(double), m);
+             "for its %d outputs%s",
+             lds_need, lds_limit, spec.mala ? user_mala_lds(spec, m) : (size_t)m * sizeof(double), m,
+             spec.mala && spec.loglike_source && spec.loglike_wave ? " and their sensitivities" : "");
     return {TDA_ERR_UNSUPPORTED, buf};
   }
   for (const UserMissingRow& row : USER_MISSING)

@@ -10,7 +10,7 @@
 // theta and out are LDS (out: n_outputs doubles, NaN before the call: an entry left unwritten rejects the proposal), `work` is
 // TDA_WORKSPACE doubles of LDS of the chain's own (a #define of the source; 0 / undefined: null), __syncthreads() inside is legal
 // and a wave barrier (one wave per workgroup).
-// Six compile options select what is built (the file itself never defines them; the signature of every function named here is
+// Seven compile options select what is built (the file itself never defines them; the signature of every function named here is
 // written once, TDA_SIG_* in tda_user_args.h):
 //   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
 //                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
@@ -18,6 +18,16 @@
 //   -DTDA_LOGLIKE_SOURCE  source-defined likelihood (TDA_NOISE_SOURCE): log L(F) = sum_o tda_loglike_term(F_o, y_o, p_o, o), defined
 //                         by the source after tda_forward; the args' `w` then carries p (not inverted).  MALA also needs
 //                         tda_loglike_term_grad, d term / d f.  The Gaussian kinds compile without it.
+//   -DTDA_LOGLIKE_WAVE    (in addition to -DTDA_LOGLIKE_SOURCE) the likelihood couples outputs: the source defines the wave form instead of
+//                         the term, tda_loglike_wave.  The outputs go through LDS (s_out[m]; a per-output model fills it first), the
+//                         chain's 64 lanes call the function together, once per evaluation, and the engine sums the 64 returns.  f is
+//                         the complete outputs in LDS, y / p the data and the parameters as given (device memory).  Every lane is called,
+//                         lanes >= n_outputs too; how the work spreads over the lanes is the function's own business
+//                         (for (o = lane; o < n_outputs; o += 64)).  No barriers, no workspace, no writes; wave shuffles are legal (the
+//                         call site is converged).  A NaN or -inf share rejects.  MALA also needs tda_loglike_grad_wave, one call by the
+//                         whole wave that writes d log L / d f_o for every output into sens (LDS, n_outputs doubles, NaN before the call:
+//                         an entry left unwritten makes the gradient NaN and rejects); the MALA program then holds 2 m doubles of
+//                         dynamic LDS, the sensitivities and behind them the outputs (a coupled gradient reads its neighbours)
 //   -DTDA_PRIOR_SOURCE    source-defined prior (tda_engine_set_prior_joint, kind TDA_PRIOR_SOURCE): log p(theta) = sum_j
 //                         tda_logprior_term(theta_j, p_j, q_j, j), defined by the source; the args' `pr_mean` / `pr_pinv` then carry
 //                         p / q as given.  tda_user_steps and the MALA kernels evaluate it (the level action carries the log-prior
@@ -57,6 +67,10 @@ TDA_FALLBACK(tda_gradient, const double*, int, const double*, int, T)
 TDA_FALLBACK(tda_loglike_term, double, double, double, T)
 TDA_FALLBACK(tda_loglike_term_grad, double, double, double, T)
 #endif
+#if defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE)
+TDA_FALLBACK(tda_loglike_wave, const double*, int, const double*, const double*, T)
+TDA_FALLBACK(tda_loglike_grad_wave, const double*, int, const double*, const double*, double*, T)
+#endif
 #ifdef TDA_PRIOR_SOURCE
 TDA_FALLBACK(tda_logprior_term, double, double, double, T)
 TDA_FALLBACK(tda_logprior_term_grad, double, double, double, T)
@@ -78,7 +92,12 @@ TDA_REQUIRE(tda_gradient_wave, "the wave form of the gradient is " TDA_SIG_GRADI
 #elif defined(TDA_USER_MALA)
 TDA_REQUIRE(tda_gradient, "MALA needs " TDA_SIG_GRADIENT, TDA_CD, 0, TDA_CD, 0, 0);
 #endif
-#ifdef TDA_LOGLIKE_SOURCE
+#if defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE)  // (the wave form stands in for the term and its derivative)
+TDA_REQUIRE(tda_loglike_wave, "the wave form of the likelihood is " TDA_SIG_LOGLIKE_WAVE, TDA_CD, 0, TDA_CD, TDA_CD, 0);
+#ifdef TDA_USER_MALA
+TDA_REQUIRE(tda_loglike_grad_wave, "MALA under TDA_LOGLIKE_WAVE needs " TDA_SIG_LOGLIKE_GRAD_WAVE, TDA_CD, 0, TDA_CD, TDA_CD, TDA_D, 0);
+#endif
+#elif defined(TDA_LOGLIKE_SOURCE)
 TDA_REQUIRE(tda_loglike_term, "a source-defined likelihood needs " TDA_SIG_LOGLIKE_TERM, 0.0, 0.0, 0.0, 0);
 #ifdef TDA_USER_MALA
 TDA_REQUIRE(tda_loglike_term_grad, "MALA needs " TDA_SIG_LOGLIKE_TERM_GRAD, 0.0, 0.0, 0.0, 0);
@@ -99,15 +118,20 @@ TDA_REQUIRE(tda_logprior_term_grad, "MALA under TDA_PRIOR_SOURCE needs " TDA_SIG
 #endif
 #endif
 
-// The wave forms' LDS: the outputs s_out[m] (dynamic, sized by the host) and the model's workspace.  A program without the
-// switches has neither: the names are null pointers that no code reads.
+// The wave forms' LDS: the outputs s_out[m] (dynamic, sized by the host; a wave-form model writes them, and a likelihood that
+// couples outputs reads them) and the model's workspace.  A program without the switches has neither: the names are null
+// pointers that no code reads.
 #if (defined(TDA_FORWARD_WAVE) || defined(TDA_GRADIENT_WAVE)) && defined(TDA_WORKSPACE) && TDA_WORKSPACE > 0
 #define TDA_DECLARE_WORK __shared__ double s_work[TDA_WORKSPACE]
 #else
 #define TDA_DECLARE_WORK double* const s_work = nullptr
 #endif
-#ifdef TDA_FORWARD_WAVE
+#if defined(TDA_FORWARD_WAVE) || (defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE))
 #define TDA_DECLARE_OUT extern __shared__ double s_out[]
+#else
+#define TDA_DECLARE_OUT double* const s_out = nullptr
+#endif
+#ifdef TDA_FORWARD_WAVE
 // every output of the model at the parameters in s_th, by one converged call of the wave; the barriers order the NaN fill, the
 // model's writes (any lane may write any entry) and the readers.  The callers' own barriers keep earlier readers of `out` away.
 __device__ __forceinline__ void tda_outputs_wave(const double* s_th, int lane, int d, int m, double* out, double* s_work) {
@@ -116,8 +140,14 @@ __device__ __forceinline__ void tda_outputs_wave(const double* s_th, int lane, i
   tda_forward_wave(s_th, d, out, m, s_work, lane);
   __syncthreads();
 }
-#else
-#define TDA_DECLARE_OUT double* const s_out = nullptr
+#endif
+#if defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE) && !defined(TDA_FORWARD_WAVE)
+// the same for a per-output model under a likelihood that couples outputs: the lanes stride over the outputs and leave them in
+// `out`, complete behind the barrier.  The callers' own barriers keep earlier readers of `out` away.
+__device__ __forceinline__ void tda_outputs_fill(const double* s_th, int lane, int d, int m, double* out) {
+  for (int o = lane; o < m; o += 64) out[o] = tda_forward(s_th, d, o);
+  __syncthreads();
+}
 #endif
 
 __device__ __forceinline__ double tda_wave_sum(double v) {
@@ -148,10 +178,17 @@ __device__ __forceinline__ double tda_loglike(const double* s_th, int lane, int 
   double sum = 0.0;
 #ifdef TDA_FORWARD_WAVE
   tda_outputs_wave(s_th, lane, d, m, s_out, s_work);
+#elif defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE)
+  (void)s_work;
+  tda_outputs_fill(s_th, lane, d, m, s_out);
 #else
   (void)s_out, (void)s_work;
 #endif
-#ifdef TDA_LOGLIKE_SOURCE
+#if defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE)
+  // a likelihood that couples outputs: one converged call by the whole wave over the complete outputs, the lanes' shares summed
+  // below; a NaN or -inf share makes the sum NaN or -inf and rejects
+  sum = tda_loglike_wave(s_out, m, data, w, lane);
+#elif defined(TDA_LOGLIKE_SOURCE)
   for (int o = lane; o < m; o += 64) sum += tda_loglike_term(TDA_OUTPUT(o), data[o], w[o], o);
 #else
   for (int o = lane; o < m; o += 64) {
@@ -365,6 +402,26 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int 
 #else
 #define TDA_MALA_OUTPUT(o) tda_forward(s_th, a.d, o)
 #endif
+#if defined(TDA_LOGLIKE_SOURCE) && defined(TDA_LOGLIKE_WAVE)
+// a likelihood that couples outputs: its gradient reads its neighbours, so the outputs are not turned into sensitivities in place.
+// The dynamic LDS is 2 m doubles, s_sens[m] and behind it the outputs s_f[m]; the model writes s_f, tda_loglike_wave gives this
+// lane's share of the sum, and tda_loglike_grad_wave writes s_sens (NaN before the call: the callers' barrier completes it).
+// `work` still holds what tda_forward_wave left, for tda_gradient_wave.
+__device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, double* s_work, int lane) {
+  double* const s_f = s_sens + a.m;
+#ifdef TDA_FORWARD_WAVE
+  tda_outputs_wave(s_th, lane, a.d, a.m, s_f, s_work);
+#else
+  (void)s_work;
+  tda_outputs_fill(s_th, lane, a.d, a.m, s_f);
+#endif
+  const double sum = tda_loglike_wave(s_f, a.m, a.data, a.w, lane);
+  for (int o = lane; o < a.m; o += 64) s_sens[o] = __builtin_nan("");
+  __syncthreads();
+  tda_loglike_grad_wave(s_f, a.m, a.data, a.w, s_sens, lane);
+  return sum;
+}
+#else
 __device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const double* s_th, double* s_sens, double* s_work, int lane) {
   double sum = 0.0;
 #ifdef TDA_FORWARD_WAVE
@@ -391,8 +448,9 @@ __device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const 
 #endif
   return sum;
 }
+#endif
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
-  extern __shared__ double s_sens[];  // [m]
+  extern __shared__ double s_sens[];  // [m] ([2 m] under TDA_LOGLIKE_WAVE: the outputs behind the sensitivities)
   __shared__ double s_th[128];
   TDA_DECLARE_WORK;
 #ifdef TDA_GRADIENT_WAVE

@@ -29,7 +29,8 @@ namespace {
 struct UserProgram {
   hipModule_t mod = nullptr;
   hipFunction_t steps = nullptr, eval = nullptr, level = nullptr, grad0 = nullptr;
-  size_t out_lds = 0;    // dynamic LDS of steps / eval / level: the outputs s_out[m] of a wave-form model (0 without one)
+  size_t out_lds = 0;    // dynamic LDS of steps / eval / level: the outputs s_out[m] of a wave-form model or likelihood (0 without one;
+                         // tda_user_eval reads it under a wave-form model only and is launched with it all the same: one size per program)
   UserProgramSpec spec;  // what it was compiled with (ensure_user_program of tda_engine.hip builds it again when that changed since)
   void unload() {
     if (mod) (void)hipModuleUnload(mod);
@@ -40,8 +41,9 @@ struct UserProgram {
 constexpr size_t USER_LDS_MAX = 64 * 1024;  // (the hardware has 160 KiB: this much needs no opt-in and keeps two chains per CU)
 
 // hiprtc for gfx950: tda_user_program.hip with the user's source and the argument structs as its named headers, under the
-// options of `spec`; a failed compile is read by diagnose_user_build.  A program with a wave form of the model holds at most
-// 64 KiB of LDS per workgroup (= per chain), static and dynamic together, for `m` outputs.
+// options of `spec`; a failed compile is read by diagnose_user_build.  A program with a wave form of the model or of the
+// likelihood holds at most 64 KiB of LDS per workgroup (= per chain), static and dynamic together, for `m` outputs (the MALA
+// program of a likelihood that couples outputs: 2 m doubles, user_mala_lds).
 int compile_user_program(const char* source, const UserProgramSpec& spec, int m, UserProgram* out) {
   const bool mala = spec.mala;
   const char* const headers[] = {source, tda_user_args_text};
@@ -73,15 +75,20 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
     HIP_TRY(hipModuleGetFunction(&out->level, out->mod, "tda_user_level_action"));
   }
   out->spec = spec;
-  out->out_lds = spec.forward_wave && !mala ? (size_t)m * sizeof(double) : 0;
-  if (spec.forward_wave || spec.gradient_wave) {  // the LDS of a chain: what the kernels declare (s_th, s_grad, the workspace) + outputs / sensitivities
-    const size_t dyn = (size_t)m * sizeof(double);
+  const bool loglike_wave = spec.loglike_source && spec.loglike_wave;
+  out->out_lds = mala ? 0 : user_dynamic_lds(spec, m);
+  if (spec.forward_wave || spec.gradient_wave || loglike_wave) {  // the LDS of a chain: what the kernels declare (s_th, s_grad, the workspace) + outputs / sensitivities
+    const size_t dyn = user_dynamic_lds(spec, m);
     for (hipFunction_t fn : {out->steps, out->eval, out->level, out->grad0}) {
       int stat = 0;
       if (!fn) continue;
       HIP_TRY(hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn));
       if ((size_t)stat + dyn > USER_LDS_MAX) {
         out->unload();
+        if (loglike_wave)
+          return fail(TDA_ERR_UNSUPPORTED, "a likelihood that couples outputs holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters, "
+                                           "gradient and TDA_WORKSPACE) + %zu bytes for its %d outputs%s",
+                      stat, dyn, m, mala ? " and their sensitivities" : "");
         return fail(TDA_ERR_UNSUPPORTED, "a wave-form model holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient and "
                                          "TDA_WORKSPACE) + %zu bytes for its %d outputs",
                     stat, dyn, m);
@@ -90,9 +97,6 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
   }
   return TDA_OK;
 }
-
-// dynamic LDS of the MALA kernels: the sensitivity of the m outputs (s_sens[m] of tda_user_program.hip)
-inline size_t user_mala_lds(const UserMalaArgs& a) { return a.m * sizeof(double); }
 
 // one wave per chain; `lds` bytes of dynamic LDS
 template <class Args>

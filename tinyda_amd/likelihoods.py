@@ -3,7 +3,7 @@
 All are *unnormalised* (-1/2 r^T Sigma^-1 r).  `GaussianLogLike` is the reference's factory: a diagonal
 covariance with equal entries becomes isotropic, a diagonal one diagonal, anything else dense
 (distributions.py:237-243).  Each class also reports how the device engine should see it (`_lowering`).
-`DeviceLogLike` (extension) is a separable log-likelihood given as HIP source, for everything that is not Gaussian;
+`DeviceLogLike` (extension) is a log-likelihood given as HIP source, separable or coupling its outputs, for everything that is not Gaussian;
 `DevicePrior` (extension) the same for a prior of independent components, and `JointPrior` lowers lists of scipy families
 through it with the term library `csrc/tda_prior_families.h`.
 """
@@ -115,7 +115,7 @@ def GaussianLogLike(data, covariance):
 
 
 class DeviceLogLike:
-    """A separable log-likelihood given as HIP source (extension; the reference takes any object with `loglike`,
+    """A log-likelihood given as HIP source, separable or coupling its outputs (extension; the reference takes any object with `loglike`,
     posterior.py:95-108, and evaluates it in Python): log L(F) = sum_o term(F_o, y_o, p_o, o).  The source must define
 
         __device__ double tda_loglike_term(double f, double y, double p, int o);        // term o
@@ -126,12 +126,41 @@ class DeviceLogLike:
 
     `data` is y, `parameters` one value per output (a scale, an exposure, a censoring limit; ones when not given);
     constants shared by all outputs are literals in the source.  The functions are pure.  A term that is NaN or -inf
-    rejects the proposal.  Likelihoods that couple outputs are not covered.  It is compiled into the program of the
-    level's `DeviceModel`, so it lowers beside such a model only.
+    rejects the proposal.  It is compiled into the program of the level's `DeviceModel`, so it lowers beside such a model only.
 
-    `reference(x, data, parameters)`, if given, returns the vector of terms in NumPy and serves `loglike` on the host
-    (host protocol, tests); `reference_gradient(x, data, parameters)` the vector of derivatives, which becomes
-    `grad_loglike` (an attribute only then, so that the host MALA takes the exact-gradient branch)."""
+    A likelihood that couples outputs (correlated noise such as AR(1) residuals, a noise level integrated out, softmax counts,
+    constraints between neighbouring outputs) defines the wave form INSTEAD of the term (a source with both is a ValueError);
+    `coupled` is then true:
+
+        __device__ double tda_loglike_wave(const double* f, int n_outputs, const double* y, const double* p, int lane);
+
+    The 64 lanes of the chain's wave call it together, once per evaluation, and the engine sums the 64 return values.  `f` holds
+    the model's outputs in LDS, complete before the call; `y` and `p` are the data and the parameters as given.  Every lane is
+    called, lanes >= n_outputs too, and the call site is converged; how the work spreads over the lanes is the function's own
+    business -- the idiom is `for (int o = lane; o < n_outputs; o += 64)`.  No barriers, no workspace, no writes.  Wave
+    shuffles are legal: a likelihood that is a non-linear function of a reduction reduces with `__shfl_xor` and returns the value
+    from one lane, 0 from the others.  The noise level integrated out, log L = -(a + m/2) log(b + 1/2 sum_o r_o^2):
+
+        __device__ double tda_loglike_wave(const double* f, int n_outputs, const double* y, const double* p, int lane) {
+          double s = 0.0;
+          for (int o = lane; o < n_outputs; o += 64) { const double r = (f[o] - y[o]) / p[o]; s += r * r; }
+          for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);       // every lane now holds the sum
+          return lane == 0 ? -(2.0 + 0.5 * n_outputs) * log(1.5 + 0.5 * s) : 0.0;  // a = 2, b = 1.5
+        }
+
+    A NaN or -inf share rejects the proposal.  It lowers wherever the separable form does and is refused in the same places.
+    Per chain the step program then holds 8 (m + 128 + TDA_WORKSPACE) bytes of LDS, the MALA program 8 (2 m + 128 +
+    TDA_WORKSPACE) (+ 1 KiB beside `tda_gradient_wave`), at most 64 KiB.  Under MALA it needs
+
+        __device__ void tda_loglike_grad_wave(const double* f, int n_outputs, const double* y, const double* p, double* sens, int lane);
+
+    one call by the whole wave that writes d log L / d f_o for every output into `sens` (LDS, NaN before the call: an entry
+    left unwritten makes the gradient NaN and rejects the proposal); `has_gradient` then refers to this function.
+
+    `reference(x, data, parameters)`, if given, returns the vector of terms in NumPy (for a coupled likelihood a scalar or any
+    array that sums to log L) and serves `loglike` on the host (host protocol, tests); `reference_gradient(x, data, parameters)`
+    the vector of derivatives d log L / d F, which becomes `grad_loglike` (an attribute only then, so that the host MALA takes
+    the exact-gradient branch)."""
 
     def __init__(self, source, data, parameters=None, reference=None, reference_gradient=None):
         self.source = str(source)
@@ -140,9 +169,15 @@ class DeviceLogLike:
                            else np.atleast_1d(np.asarray(parameters, dtype=np.float64)))
         if self.data.ndim != 1 or self.parameters.shape != self.data.shape:
             raise ValueError("data and parameters must be vectors with one entry per model output")
-        if not _defines(self.source, "tda_loglike_term"):
-            raise ValueError("the source must define __device__ double tda_loglike_term(double f, double y, double p, int o)")
-        self.has_gradient = _defines(self.source, "tda_loglike_term_grad")
+        term = _defines(self.source, "tda_loglike_term")
+        self.coupled = _defines(self.source, "tda_loglike_wave")
+        if term and self.coupled:
+            raise ValueError("the source defines both tda_loglike_term and tda_loglike_wave: a likelihood has one form")
+        if not term and not self.coupled:
+            raise ValueError("the source must define __device__ double tda_loglike_term(double f, double y, double p, int o) (or, for a "
+                             "likelihood that couples outputs, __device__ double tda_loglike_wave(const double* f, int n_outputs, "
+                             "const double* y, const double* p, int lane))")
+        self.has_gradient = _defines(self.source, "tda_loglike_grad_wave" if self.coupled else "tda_loglike_term_grad")
         self.reference = reference
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:

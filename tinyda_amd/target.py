@@ -102,7 +102,7 @@ class Posterior:
                        has_forward_wave=self.model.has_forward_wave, has_gradient_wave=self.model.has_gradient_wave, data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
             if kind == _lib.NOISE_SOURCE:  # DeviceLogLike: its functions are compiled with the model, one program
                 low.update(source=self.model.source + "\n" + self.likelihood.source, loglike_source=True,
-                           loglike_has_gradient=self.likelihood.has_gradient)
+                           loglike_has_gradient=self.likelihood.has_gradient, loglike_coupled=bool(getattr(self.likelihood, "coupled", False)))
             return low
         if isinstance(self.model, BatchedModel):
             kind, noise = self.likelihood._lowering()

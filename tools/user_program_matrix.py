@@ -4,7 +4,7 @@ normalised assembly (tests/extprogram.assembly).  Two program texts with equal t
 
     python tools/user_program_matrix.py [program.hip]          (default: the shipped csrc/tda_user_program.hip)
 
-Step program: likelihood {gauss, source} x prior {engine, term, wave} x model {per_output, wave}; MALA program: the same x
+Step program: likelihood {gauss, source, wave} x prior {engine, term, wave} x model {per_output, wave}; MALA program: the same x
 gradient {per_parameter, wave}.  The user sources are the ones tests/ext*.py hold; a combination they hold none for is listed
 as such."""
 import hashlib
@@ -17,6 +17,7 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tests import extloglike as xl  # noqa: E402
+from tests import extloglikewave as xlw  # noqa: E402
 from tests import extmodel as xm  # noqa: E402
 from tests import extprior as xp  # noqa: E402
 from tests import extprogram  # noqa: E402
@@ -25,7 +26,8 @@ from tests import extwave as xw  # noqa: E402
 from tests.extpriorgrad import LOGNORMAL_GRAD_SRC  # noqa: E402
 
 M = 23  # (the per-output form of tests/extwave.py has the number of outputs written in)
-LIKELIHOODS = {"gauss": ("", []), "source": (xl.KINDS["t"][0], ["TDA_LOGLIKE_SOURCE"])}
+LIKELIHOODS = {"gauss": ("", []), "source": (xl.KINDS["t"][0], ["TDA_LOGLIKE_SOURCE"]),
+               "wave": (xlw.MARGINAL_SRC, ["TDA_LOGLIKE_SOURCE", "TDA_LOGLIKE_WAVE"])}
 PRIORS = {"engine": ("", []), "term": (xp.LOGNORMAL_SRC + LOGNORMAL_GRAD_SRC, ["TDA_PRIOR_SOURCE"]),
           "wave": (xpw.CAUCHY_DIFF_SRC, ["TDA_PRIOR_SOURCE", "TDA_PRIOR_WAVE"])}
 MODELS = {"per_output": [], "wave": ["TDA_FORWARD_WAVE"]}
