@@ -70,6 +70,15 @@ def test_scan_is_the_same_in_the_engine_and_in_python(tool, what, source, name, 
     assert _defines(source, name) is defined
 
 
+def test_signatures_are_the_same_in_the_engine_and_in_python(tool):
+    """TDA_SIG_* of csrc/tda_user_args.h against tinyda_amd._contract.SIG; tda_forward has no macro"""
+    from tinyda_amd._contract import SIG
+
+    printed = dict(ln.split("\t") for ln in tool("signatures").splitlines())
+    assert printed == {name: text for name, text in SIG.items() if name != "tda_forward"} and len(printed) == 11
+    assert all(text.startswith("__device__ ") and " %s(" % name in text for name, text in SIG.items())
+
+
 def test_python_classes_decide_as_the_engine_does(tool):
     """the two sources on which the classes used to disagree with the engine"""
     import tinyda_amd as tda

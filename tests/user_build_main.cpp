@@ -4,6 +4,7 @@
 //   forms FILE                             the six UserForms flags and the "both forms" decision
 //   options                                every spec, one line each: its five fields, a colon, its option list
 //   diagnose MALA LOGLIKE PRIOR FW GW M FILE   the error code, a newline, the message for the compiler log in FILE
+//   signatures                             the contract's signatures (TDA_SIG_* in csrc/tda_user_args.h), one line each: the function's name, a tab, the text
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -38,8 +39,17 @@ int main(int argc, char** argv) {
     s.mala = atoi(argv[2]), s.loglike_source = atoi(argv[3]), s.prior_form = atoi(argv[4]), s.forward_wave = atoi(argv[5]), s.gradient_wave = atoi(argv[6]);
     const UserBuildError err = diagnose_user_build(slurp(argv[8]), s, atoi(argv[7]));
     std::cout << err.code << "\n" << err.message;
+  } else if (cmd == "signatures" && argc == 2) {
+    const char* const sigs[][2] = {
+        {"tda_forward_wave", TDA_SIG_FORWARD_WAVE},   {"tda_gradient_wave", TDA_SIG_GRADIENT_WAVE},
+        {"tda_gradient", TDA_SIG_GRADIENT},           {"tda_loglike_term", TDA_SIG_LOGLIKE_TERM},
+        {"tda_loglike_term_grad", TDA_SIG_LOGLIKE_TERM_GRAD}, {"tda_loglike_wave", TDA_SIG_LOGLIKE_WAVE},
+        {"tda_loglike_grad_wave", TDA_SIG_LOGLIKE_GRAD_WAVE}, {"tda_logprior_term", TDA_SIG_LOGPRIOR_TERM},
+        {"tda_logprior_term_grad", TDA_SIG_LOGPRIOR_TERM_GRAD}, {"tda_logprior_wave", TDA_SIG_LOGPRIOR_WAVE},
+        {"tda_logprior_grad", TDA_SIG_LOGPRIOR_GRAD}};
+    for (const auto& sig : sigs) std::cout << sig[0] << "\t" << sig[1] << "\n";
   } else {
-    std::cerr << "usage: scan NAME FILE | forms FILE | options | diagnose MALA LOGLIKE PRIOR FW GW M FILE\n";
+    std::cerr << "usage: scan NAME FILE | forms FILE | options | signatures | diagnose MALA LOGLIKE PRIOR FW GW M FILE\n";
     return 2;
   }
   return 0;

@@ -12,7 +12,12 @@ import os
 import numpy as np
 
 from . import _lib
+from ._contract import SIG
 from .models import _defines
+
+
+def _is_diagonal(cov):
+    return np.count_nonzero(cov - np.diag(np.diag(cov))) == 0
 
 
 def _check_covariance(data, covariance):
@@ -106,9 +111,8 @@ class AdaptiveGaussianLogLike(DefaultGaussianLogLike):
 def GaussianLogLike(data, covariance):
     """Factory with the reference's dispatch and error behaviour (distributions.py:203-243)."""
     _check_covariance(data, covariance)
-    diagonal = np.diag(covariance)
-    if np.count_nonzero(covariance - np.diag(diagonal)) == 0:
-        if np.all(diagonal == covariance[0, 0]):
+    if _is_diagonal(covariance):
+        if np.all(np.diag(covariance) == covariance[0, 0]):
             return IsotropicGaussianLogLike(data, covariance[0, 0])
         return DiagonalGaussianLogLike(data, covariance)
     return DefaultGaussianLogLike(data, covariance)
@@ -174,9 +178,7 @@ class DeviceLogLike:
         if term and self.coupled:
             raise ValueError("the source defines both tda_loglike_term and tda_loglike_wave: a likelihood has one form")
         if not term and not self.coupled:
-            raise ValueError("the source must define __device__ double tda_loglike_term(double f, double y, double p, int o) (or, for a "
-                             "likelihood that couples outputs, __device__ double tda_loglike_wave(const double* f, int n_outputs, "
-                             "const double* y, const double* p, int lane))")
+            raise ValueError("the source must define %s (or, for a likelihood that couples outputs, %s)" % (SIG["tda_loglike_term"], SIG["tda_loglike_wave"]))
         self.has_gradient = _defines(self.source, "tda_loglike_grad_wave" if self.coupled else "tda_loglike_term_grad")
         self.reference = reference
         self.reference_gradient = reference_gradient
@@ -255,9 +257,7 @@ class DevicePrior:
         if term and self.coupled:
             raise ValueError("the source defines both tda_logprior_term and tda_logprior_wave: a prior has one form")
         if not term and not self.coupled:
-            raise ValueError("the source must define __device__ double tda_logprior_term(double x, double p, double q, int j) (or, for a "
-                             "prior that couples parameters, __device__ double tda_logprior_wave(const double* theta, int dim, "
-                             "const double* p, const double* q, int lane))")
+            raise ValueError("the source must define %s (or, for a prior that couples parameters, %s)" % (SIG["tda_logprior_term"], SIG["tda_logprior_wave"]))
         self.has_gradient = _defines(self.source, "tda_logprior_grad" if self.coupled else "tda_logprior_term_grad")
         self.reference = reference
         self.reference_gradient = reference_gradient

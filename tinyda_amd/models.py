@@ -7,6 +7,8 @@ import re
 
 import numpy as np
 
+from ._contract import SIG
+
 
 class LinearModel:
     """F(theta) = A theta (+ b).  All BASELINE.json configurations use linear forward models."""
@@ -81,8 +83,7 @@ class DeviceModel:
         self.has_forward_wave = _defines(self.source, "tda_forward_wave")
         self.has_gradient_wave = _defines(self.source, "tda_gradient_wave")
         if not (self.has_forward_wave or _defines(self.source, "tda_forward")):
-            raise ValueError("the source must define __device__ double tda_forward(const double* theta, int dim, int o) or __device__ void "
-                             "tda_forward_wave(const double* theta, int dim, double* out, int n_outputs, double* work, int lane)")
+            raise ValueError("the source must define %s or %s" % (SIG["tda_forward"], SIG["tda_forward_wave"]))
         self.has_gradient = self.has_gradient_wave or _defines(self.source, "tda_gradient")
         self.reference_gradient = reference_gradient
         if reference_gradient is not None:

@@ -86,33 +86,26 @@ class Posterior:
             return None
         mean = np.atleast_1d(np.asarray(mean, dtype=np.float64))
         cov = np.atleast_2d(np.asarray(cov, dtype=np.float64))
+        kind, noise = self.likelihood._lowering()
+        noise = np.asarray(noise, dtype=np.float64)
+        data = np.asarray(self.likelihood.data, dtype=np.float64)
+        if isinstance(self.model, LinearModel):
+            if self.model.A.shape[1] != mean.shape[0]:
+                return None
+            return dict(prior_mean=mean, prior_cov=cov, A=self.model.A, b=self.model.b, data=data, noise_kind=kind, noise=noise)
+        data = np.atleast_1d(data)
+        low = dict(prior_mean=mean, prior_cov=cov, A=None, b=None, data=data, noise_kind=kind, noise=noise)
         if isinstance(self.model, Rosenbrock):
-            kind, noise = self.likelihood._lowering()
-            data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
             if data.shape != (1,) or np.size(noise) != 1 or mean.shape[0] < 2:
                 return None
-            return dict(prior_mean=mean, prior_cov=cov, rosenbrock=(self.model.a, self.model.b), A=None, b=None, data=data,
-                        noise_kind=kind, noise=np.asarray(noise, dtype=np.float64).reshape(1))
-        if isinstance(self.model, DeviceModel):
-            kind, noise = self.likelihood._lowering()
-            data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
-            if data.shape != (self.model.n_outputs,):
-                return None
-            low = dict(prior_mean=mean, prior_cov=cov, source=self.model.source, has_gradient=self.model.has_gradient, A=None, b=None,
-                       has_forward_wave=self.model.has_forward_wave, has_gradient_wave=self.model.has_gradient_wave, data=data, noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
-            if kind == _lib.NOISE_SOURCE:  # DeviceLogLike: its functions are compiled with the model, one program
-                low.update(source=self.model.source + "\n" + self.likelihood.source, loglike_source=True,
-                           loglike_has_gradient=self.likelihood.has_gradient, loglike_coupled=bool(getattr(self.likelihood, "coupled", False)))
-            return low
-        if isinstance(self.model, BatchedModel):
-            kind, noise = self.likelihood._lowering()
-            data = np.atleast_1d(np.asarray(self.likelihood.data, dtype=np.float64))
-            if data.shape != (self.model.n_outputs,):
-                return None
-            return dict(prior_mean=mean, prior_cov=cov, batched=self.model.batch, A=None, b=None, data=data,
-                        noise_kind=kind, noise=np.asarray(noise, dtype=np.float64))
-        if self.model.A.shape[1] != mean.shape[0]:
+            return dict(low, rosenbrock=(self.model.a, self.model.b), noise=noise.reshape(1))
+        if data.shape != (self.model.n_outputs,):
             return None
-        kind, noise = self.likelihood._lowering()
-        return dict(prior_mean=mean, prior_cov=cov, A=self.model.A, b=self.model.b,
-                    data=np.asarray(self.likelihood.data, dtype=np.float64), noise_kind=kind, noise=noise)
+        if isinstance(self.model, BatchedModel):
+            return dict(low, batched=self.model.batch)
+        low.update(source=self.model.source, has_gradient=self.model.has_gradient, has_forward_wave=self.model.has_forward_wave,
+                   has_gradient_wave=self.model.has_gradient_wave)
+        if kind == _lib.NOISE_SOURCE:  # DeviceLogLike: its functions are compiled with the model, one program
+            low.update(source=self.model.source + "\n" + self.likelihood.source, loglike_source=True,
+                       loglike_has_gradient=self.likelihood.has_gradient, loglike_coupled=bool(getattr(self.likelihood, "coupled", False)))
+        return low
