@@ -27,4 +27,5 @@ from .proposals import (  # noqa: F401
     OperatorWeightedCrankNicolson, Proposal)
 from .records import DeviceChain  # noqa: F401
 from .api import HostFallbackWarning, release_cached_memory, sample  # noqa: F401
+from .replay import Replay, replay_records  # noqa: F401
 from .moments import RecursiveSampleMoments, ZeroMeanRecursiveSampleMoments  # noqa: F401

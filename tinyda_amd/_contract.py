@@ -15,3 +15,9 @@ SIG = {
     "tda_logprior_wave": "__device__ double tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane)",
     "tda_logprior_grad": "__device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j)",
 }
+
+# the quantity of interest of a DeviceModel (TDA_SIG_QOI / TDA_SIG_QOI_WAVE; tests/test_replay.py compares the two sides)
+QOI_SIG = {
+    "tda_qoi": "__device__ double tda_qoi(const double* theta, int dim, const double* f, int n_outputs, int k)",
+    "tda_qoi_wave": "__device__ void tda_qoi_wave(const double* theta, int dim, const double* f, int n_outputs, double* qoi, int n_qoi, double* work, int lane)",
+}

@@ -160,6 +160,13 @@ SYMBOLS = {
     "tda_engine_get_profile": (C.c_int, [_P, C.POINTER(tda_profile)]),
 }
 
+# every symbol include/tinyda_amd_replay.h declares: bound by load() only (the CPU twin of the ABI, load_from, has no replay)
+REPLAY_SYMBOLS = {
+    "tda_replay_create": (C.c_int, [C.c_int, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "tda_replay_run": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_int64), _P]),
+    "tda_replay_destroy": (None, [_P]),
+}
+
 _lib = None
 
 
@@ -201,7 +208,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # missing ROCm runtime etc.
         raise EngineError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -18,6 +18,9 @@
 #define TDA_CALL_LOGPRIOR_WAVE "tda_logprior_wave(const double* theta, int dim, const double* p, const double* q, int lane)"
 #define TDA_SIG_LOGPRIOR_WAVE "__device__ double " TDA_CALL_LOGPRIOR_WAVE
 #define TDA_SIG_LOGPRIOR_GRAD "__device__ double tda_logprior_grad(const double* theta, int dim, const double* p, const double* q, int j)"
+#define TDA_SIG_QOI "__device__ double tda_qoi(const double* theta, int dim, const double* f, int n_outputs, int k)"
+#define TDA_SIG_QOI_WAVE \
+  "__device__ void tda_qoi_wave(const double* theta, int dim, const double* f, int n_outputs, double* qoi, int n_qoi, double* work, int lane)"
 
 struct UserStepArgs {
   long long N, NP;
@@ -92,4 +95,15 @@ struct UserMalaArgs {
   double* rec_params;
   double* rec_stats;
   unsigned char* rec_acc;
+};
+
+// The replay of recorded parameters through the model (tda_user_replay): outputs and quantities of interest of the rows
+// [0, R) of N chains, one wave per chain and segment of `seg` rows.  Either destination may be null.
+struct UserReplayArgs {
+  long long N, R, seg;
+  int d, m, nq;
+  const double* params;  // [R][N][d]
+  double* outputs;       // [R][N][m] or null
+  double* qoi;           // [R][N][nq] or null
+  long long* n_eval;     // model evaluations, added to (may be null)
 };

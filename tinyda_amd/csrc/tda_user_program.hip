@@ -10,8 +10,8 @@
 // theta and out are LDS (out: n_outputs doubles, NaN before the call: an entry left unwritten rejects the proposal), `work` is
 // TDA_WORKSPACE doubles of LDS of the chain's own (a #define of the source; 0 / undefined: null), __syncthreads() inside is legal
 // and a wave barrier (one wave per workgroup).
-// Seven compile options select what is built (the file itself never defines them; the signature of every function named here is
-// written once, TDA_SIG_* in tda_user_args.h):
+// Compile options select what is built (the file itself never defines them; the signature of every function named here is
+// written once, TDA_SIG_* in tda_user_args.h).  Seven for the programs that sample:
 //   -DTDA_USER_MALA       the MALA kernels (tda_user_mala_steps, tda_user_mala_grad0) instead of tda_user_steps,
 //                         tda_user_level_action and tda_user_eval.  MALA (0.5) needs the model's vector-Jacobian product,
 //                         tda_gradient = (J(theta)^T sensitivity)_j (the reference's model.gradient(parameters, sensitivity), proposal.py:996-998)
@@ -43,6 +43,15 @@
 //                         lets the model write into its s_sens[m]) after one call, not from tda_forward(theta, dim, o) per output
 //   -DTDA_GRADIENT_WAVE   (MALA program) the source defines the vector-Jacobian product in the same form, tda_gradient_wave, one call for all
 //                         parameters.  grad: LDS, 128 doubles, zero before the call; `work` is what tda_forward_wave left at the same theta
+// and three more select a third program, which runs after the sampling, over its records:
+//   -DTDA_USER_REPLAY     the replay kernel (tda_user_replay) instead of the step kernels: outputs and quantities of interest of
+//                         recorded parameters.  -DTDA_FORWARD_WAVE applies as above
+//   -DTDA_QOI             (replay program) the source defines a quantity of interest per call, tda_qoi: quantity k of n_qoi from
+//                         theta and the complete outputs f (both LDS); the lanes stride over k
+//   -DTDA_QOI_WAVE        (replay program) the source defines all quantities in one call by the chain's 64 lanes, tda_qoi_wave
+//                         (converged call site, __syncthreads() legal).  qoi: LDS, n_qoi doubles, NaN before the call (an entry
+//                         left unwritten stays NaN: a NaN quantity is data, nothing is rejected here); `work` is what
+//                         tda_forward_wave left at the same theta (null without TDA_WORKSPACE)
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -78,6 +87,11 @@ TDA_FALLBACK(tda_logprior_term_grad, double, double, double, T)
 #if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
 TDA_FALLBACK(tda_logprior_wave, const double*, int, const double*, const double*, T)
 TDA_FALLBACK(tda_logprior_grad, const double*, int, const double*, const double*, T)
+#endif
+#if defined(TDA_USER_REPLAY) && defined(TDA_QOI_WAVE)
+TDA_FALLBACK(tda_qoi_wave, const double*, int, const double*, int, double*, int, double*, T)
+#elif defined(TDA_USER_REPLAY) && defined(TDA_QOI)
+TDA_FALLBACK(tda_qoi, const double*, int, const double*, int, T)
 #endif
 
 #include "tda_user_source.h"
@@ -116,6 +130,11 @@ TDA_REQUIRE(tda_logprior_term, "a source-defined prior needs " TDA_SIG_LOGPRIOR_
 TDA_REQUIRE(tda_logprior_term_grad, "MALA under TDA_PRIOR_SOURCE needs " TDA_SIG_LOGPRIOR_TERM_GRAD, 0.0, 0.0, 0.0, 0);
 #endif
 #endif
+#endif
+#if defined(TDA_USER_REPLAY) && defined(TDA_QOI_WAVE)
+TDA_REQUIRE(tda_qoi_wave, "the wave form of the quantity of interest is " TDA_SIG_QOI_WAVE, TDA_CD, 0, TDA_CD, 0, TDA_D, 0, TDA_D, 0);
+#elif defined(TDA_USER_REPLAY) && defined(TDA_QOI)
+TDA_REQUIRE(tda_qoi, "a quantity of interest is " TDA_SIG_QOI, TDA_CD, 0, TDA_CD, 0, 0);
 #endif
 
 // The wave forms' LDS: the outputs s_out[m] (dynamic, sized by the host; a wave-form model writes them, and a likelihood that
@@ -165,7 +184,70 @@ __device__ __forceinline__ double tda_loglike_of_sum(double sum, const double* w
 #endif
 }
 
-#ifndef TDA_USER_MALA
+#ifdef TDA_USER_REPLAY
+// Outputs and quantities of interest of recorded parameters, after the run: the forward model is deterministic, so the records
+// [R][N][d] hold everything that the reference's Link carries beside them (link.py:23-48: model_output, qoi).  One wave per
+// chain c and segment of rows [r0, r1): the wave walks its rows in order and keeps the previous row in registers; a rejected
+// step repeats its predecessor's parameters bit for bit, so a row whose integer image equals the previous row's (one wave vote;
+// -0.0 differs from 0.0, a NaN equals itself) takes the outputs and quantities that already stand in LDS, and the model runs
+// once per accepted state, not once per row.  The test is on the parameters, not on the accept flags: it holds under thinning and
+// on every level of a hierarchy.  Dynamic LDS: the outputs s_out[m] and behind them the quantities s_qoi[nq].
+#if (defined(TDA_FORWARD_WAVE) || defined(TDA_QOI_WAVE)) && defined(TDA_WORKSPACE) && TDA_WORKSPACE > 0
+#define TDA_DECLARE_REPLAY_WORK __shared__ double s_work[TDA_WORKSPACE]
+#else
+#define TDA_DECLARE_REPLAY_WORK double* const s_work = nullptr
+#endif
+extern "C" __global__ void __launch_bounds__(64) tda_user_replay(const UserReplayArgs a) {
+  extern __shared__ double s_out[];
+  __shared__ double s_th[128];  // (65 .. 128 parameters: a lane holds parameters `lane` and `lane + 64`)
+  TDA_DECLARE_REPLAY_WORK;
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x % a.N, r0 = blockIdx.x / a.N * a.seg;
+  const long long r1 = r0 + a.seg < a.R ? r0 + a.seg : a.R;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  double* const s_qoi = s_out + a.m;
+  long long prev = 0, prev2 = 0;
+  long long neval = 0;
+  for (long long r = r0; r < r1; ++r) {
+    const size_t row = (size_t)r * a.N + c;
+    const double th = lj ? a.params[row * a.d + lane] : 0.0, th2 = lj2 ? a.params[row * a.d + lane2] : 0.0;
+    const long long bits = __double_as_longlong(th), bits2 = __double_as_longlong(th2);
+    if (r == r0 || __any(bits != prev || bits2 != prev2)) {
+      __syncthreads();  // (the previous row's stores have read s_out / s_qoi)
+      s_th[lane] = th;
+      s_th[lane2] = th2;
+      __syncthreads();
+#ifdef TDA_FORWARD_WAVE
+      tda_outputs_wave(s_th, lane, a.d, a.m, s_out, s_work);
+#else
+      for (int o = lane; o < a.m; o += 64) s_out[o] = tda_forward(s_th, a.d, o);  // (the order in which tda_user_eval strides)
+      __syncthreads();
+#endif
+#ifdef TDA_QOI_WAVE
+      // all quantities by one converged call of the wave; a NaN is data here, an entry left unwritten stays NaN
+      for (int k = lane; k < a.nq; k += 64) s_qoi[k] = __builtin_nan("");
+      __syncthreads();
+      tda_qoi_wave(s_th, a.d, s_out, a.m, s_qoi, a.nq, s_work, lane);
+      __syncthreads();
+#elif defined(TDA_QOI)
+      for (int k = lane; k < a.nq; k += 64) s_qoi[k] = tda_qoi(s_th, a.d, s_out, a.m, k);
+      __syncthreads();
+#endif
+      ++neval;
+    }
+    prev = bits;
+    prev2 = bits2;
+    if (a.outputs)
+      for (int o = lane; o < a.m; o += 64) a.outputs[row * a.m + o] = s_out[o];
+#if defined(TDA_QOI_WAVE) || defined(TDA_QOI)
+    if (a.qoi)
+      for (int k = lane; k < a.nq; k += 64) a.qoi[row * a.nq + k] = s_qoi[k];
+#endif
+  }
+  if (lane == 0 && a.n_eval) atomicAdd((unsigned long long*)a.n_eval, (unsigned long long)neval);
+}
+
+#elif !defined(TDA_USER_MALA)
 // log-likelihood of the model outputs at the parameters in s_th, for the whole wave (link.py:48 takes any loglike).  The level's
 // fields come in one by one: with the argument struct passed whole the kernels no longer compile to the instructions they had.
 #ifdef TDA_FORWARD_WAVE

@@ -25,10 +25,11 @@ extern "C" const char tda_user_args_text[] __attribute__((visibility("hidden")))
 
 namespace {
 
-// one compiled program of a level: the step program (steps, eval, level) or the MALA program (steps, grad0)
+// one compiled program of a level: the step program (steps, eval, level) or the MALA program (steps, grad0); or, of no level
+// and no engine, the replay program (replay: tda_host_replay.inc)
 struct UserProgram {
   hipModule_t mod = nullptr;
-  hipFunction_t steps = nullptr, eval = nullptr, level = nullptr, grad0 = nullptr;
+  hipFunction_t steps = nullptr, eval = nullptr, level = nullptr, grad0 = nullptr, replay = nullptr;
   size_t out_lds = 0;    // dynamic LDS of steps / eval / level: the outputs s_out[m] of a wave-form model or likelihood (0 without one;
                          // tda_user_eval reads it under a wave-form model only and is launched with it all the same: one size per program)
   UserProgramSpec spec;  // what it was compiled with (ensure_user_program of tda_engine.hip builds it again when that changed since)
@@ -43,13 +44,14 @@ constexpr size_t USER_LDS_MAX = 64 * 1024;  // (the hardware has 160 KiB: this m
 // hiprtc for gfx950: tda_user_program.hip with the user's source and the argument structs as its named headers, under the
 // options of `spec`; a failed compile is read by diagnose_user_build.  A program with a wave form of the model or of the
 // likelihood holds at most 64 KiB of LDS per workgroup (= per chain), static and dynamic together, for `m` outputs (the MALA
-// program of a likelihood that couples outputs: 2 m doubles, user_mala_lds).
-int compile_user_program(const char* source, const UserProgramSpec& spec, int m, UserProgram* out) {
+// program of a likelihood that couples outputs: 2 m doubles, user_mala_lds).  The replay program holds its m outputs and its
+// n_qoi quantities in every form, under the same rule.
+int compile_user_program(const char* source, const UserProgramSpec& spec, int m, UserProgram* out, int n_qoi = 0) {
   const bool mala = spec.mala;
   const char* const headers[] = {source, tda_user_args_text};
   const char* const names[] = {"tda_user_source.h", "tda_user_args.h"};
   hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, tda_user_program_text, mala ? "tda_user_mala.hip" : "tda_user_model.hip", 2, headers, names) != HIPRTC_SUCCESS)
+  if (hiprtcCreateProgram(&prog, tda_user_program_text, spec.replay ? "tda_user_replay.hip" : mala ? "tda_user_mala.hip" : "tda_user_model.hip", 2, headers, names) != HIPRTC_SUCCESS)
     return fail(TDA_ERR_HIP, "hiprtcCreateProgram failed");
   std::vector<const char*> opts = user_program_options(spec);
   if (hiprtcCompileProgram(prog, (int)opts.size(), opts.data()) != HIPRTC_SUCCESS) {
@@ -67,6 +69,21 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
   (void)hiprtcGetCode(prog, code.data());
   (void)hiprtcDestroyProgram(&prog);
   HIP_TRY(hipModuleLoadData(&out->mod, code.data()));
+  if (spec.replay) {
+    HIP_TRY(hipModuleGetFunction(&out->replay, out->mod, "tda_user_replay"));
+    out->spec = spec;
+    out->out_lds = user_replay_lds(m, n_qoi);
+    int stat = 0;
+    HIP_TRY(hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, out->replay));
+    if ((size_t)stat + out->out_lds > USER_LDS_MAX) {
+      const size_t dyn = out->out_lds;
+      out->unload();
+      return fail(TDA_ERR_UNSUPPORTED, "the replay of a source-defined model holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters and "
+                                       "TDA_WORKSPACE) + %zu bytes for its %d outputs and its %d quantities of interest (%zu of them for the quantities)",
+                  stat, dyn, m, n_qoi, (size_t)n_qoi * sizeof(double));
+    }
+    return TDA_OK;
+  }
   HIP_TRY(hipModuleGetFunction(&out->steps, out->mod, mala ? "tda_user_mala_steps" : "tda_user_steps"));
   if (mala) {
     HIP_TRY(hipModuleGetFunction(&out->grad0, out->mod, "tda_user_mala_grad0"));

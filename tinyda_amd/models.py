@@ -7,7 +7,7 @@ import re
 
 import numpy as np
 
-from ._contract import SIG
+from ._contract import QOI_SIG, SIG
 
 
 class LinearModel:
@@ -71,15 +71,43 @@ class DeviceModel:
     `has_forward_wave` / `has_gradient_wave` say whether the source defines the wave forms, `has_gradient` whether it defines
     either gradient (comments do not count).
 
+    With `n_qoi` > 0 the source also defines the model's quantity of interest (the reference's models return it beside the
+    output, posterior.py:97-101), in one of two forms; either goes with either form of the model, and the wave form is used when
+    both are there (`has_qoi` / `has_qoi_wave`):
+
+        // quantity k of n_qoi; f: the model's complete outputs at theta (LDS); the lanes stride over k
+        __device__ double tda_qoi(const double* theta, int dim, const double* f, int n_outputs, int k);
+        // all quantities in one call by the chain's 64 lanes (converged call site; __syncthreads() legal); qoi: LDS, n_qoi doubles,
+        // NaN before the call (an entry left unwritten stays NaN); work: what tda_forward_wave left at the same theta (null
+        // without TDA_WORKSPACE) -- the solver's state, which is where a quantity of interest usually lives
+        __device__ void tda_qoi_wave(const double* theta, int dim, const double* f, int n_outputs, double* qoi, int n_qoi, double* work, int lane);
+
+    A NaN quantity is data, not a rejection.  The step kernels never call these functions: outputs and quantities of the recorded
+    rows are produced after the run, when somebody asks (get_samples(..., "model_output" | "qoi"), to_inference_data,
+    DeviceChain.model_output / .qoi), by replaying the model over the records on the device (tinyda_amd/replay.py); `evaluate`
+    is the same at any parameters.  LDS per chain there: 8 (n_outputs + n_qoi + 128 + TDA_WORKSPACE) bytes, at most 64 KiB.
+
     `reference`, if given, is a Python callable theta -> outputs used when the model is called on the host (host
     protocol, tests); without it the model only runs on the device.  `reference_gradient(theta, sensitivity)`, if
     given, becomes the model's `gradient` method, so the host MALA takes the exact-gradient branch (finite differences
-    otherwise)."""
+    otherwise).  `reference_qoi(theta, output) -> n_qoi values`, if given, makes the host call return `(output, qoi)`, the
+    reference's model protocol, so the host protocol records the quantity too."""
 
-    def __init__(self, source, n_outputs, reference=None, reference_gradient=None):
+    def __init__(self, source, n_outputs, n_qoi=0, reference=None, reference_gradient=None, reference_qoi=None):
         self.source = str(source)
         self.n_outputs = int(n_outputs)
+        self.n_qoi = int(n_qoi)
         self.reference = reference
+        self.reference_qoi = reference_qoi
+        self.has_qoi_wave = _defines(self.source, "tda_qoi_wave")
+        self.has_qoi = self.has_qoi_wave or _defines(self.source, "tda_qoi")
+        if self.n_qoi < 0:
+            raise ValueError("n_qoi must be >= 0")
+        if self.n_qoi > 0 and not self.has_qoi:
+            raise ValueError("n_qoi = %d: the source must define %s or %s" % (self.n_qoi, QOI_SIG["tda_qoi"], QOI_SIG["tda_qoi_wave"]))
+        if self.n_qoi == 0 and self.has_qoi:
+            raise ValueError("the source defines %s: give n_qoi, the number of quantities"
+                             % QOI_SIG["tda_qoi_wave" if self.has_qoi_wave else "tda_qoi"])
         self.has_forward_wave = _defines(self.source, "tda_forward_wave")
         self.has_gradient_wave = _defines(self.source, "tda_gradient_wave")
         if not (self.has_forward_wave or _defines(self.source, "tda_forward")):
@@ -96,7 +124,21 @@ class DeviceModel:
     def __call__(self, parameters):
         if self.reference is None:
             raise TypeError("this DeviceModel has no host reference implementation; run it with backend='hip'")
-        return np.atleast_1d(np.asarray(self.reference(np.asarray(parameters, dtype=np.float64)), dtype=np.float64))
+        theta = np.asarray(parameters, dtype=np.float64)
+        out = np.atleast_1d(np.asarray(self.reference(theta), dtype=np.float64))
+        if self.reference_qoi is None:
+            return out
+        return out, np.atleast_1d(np.asarray(self.reference_qoi(theta, out), dtype=np.float64))
+
+    def __getstate__(self):  # (copies and pickles leave the compiled replay programs behind: handles of this process)
+        return {k: v for k, v in self.__dict__.items() if k != "_replays"}
+
+    def evaluate(self, thetas, device=0):
+        """F at every row of `thetas` [n, dim] on the device: outputs [n, n_outputs], or (outputs, qoi [n, n_qoi]) when the model
+        has a quantity of interest -- the posterior predictive at any parameters.  (A replay of one row of n chains.)"""
+        from .replay import evaluate
+
+        return evaluate(self, thetas, device)
 
 
 _TOKEN = re.compile(r"""//[^\n]*|/\*.*?(?:\*/|\Z)|"(?:\\.?|[^"\\])*(?:"|\Z)|'(?:\\.?|[^'\\])*(?:'|\Z)|([A-Za-z0-9_]+)""", re.S)

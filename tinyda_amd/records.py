@@ -203,6 +203,35 @@ class DeviceChain(Sequence):
     def accepted(self):  # [T+1] (entry 0 is the initial link, True as in chain.py:71)
         return self._get("accepted")
 
+    def _replayed(self, field):
+        """model outputs / quantities of interest of this chain's rows, [T+1, width]: the chain's DeviceModel replayed over its
+        parameters on the device (tinyda_amd/replay.py) and kept"""
+        from .models import DeviceModel
+
+        if not isinstance(self._model, DeviceModel):
+            raise AttributeError("%s of a whole chain needs a DeviceModel (other models: chain[i].%s, one host call per row)" % (field, field))
+        if field == "qoi" and self._model.n_qoi == 0:
+            raise AttributeError("this chain's model has no quantity of interest (n_qoi = 0)")
+        if self._cache is None:
+            self._cache = {}
+        if field not in self._cache:
+            from . import replay
+
+            if self._records is not None:
+                self._cache[field] = replay.chain_rows(self._records, self._chain, self._rows, self._model, field)
+            else:
+                theta = np.ascontiguousarray(self.parameters, dtype=np.float64)
+                self._cache[field] = replay.replay_records(theta[:, None, :], self._model, (field,))[field][0]
+        return self._cache[field]
+
+    @property
+    def model_output(self):  # [T+1, n_outputs]
+        return self._replayed("model_output")
+
+    @property
+    def qoi(self):  # [T+1, n_qoi]
+        return self._replayed("qoi")
+
     def __len__(self):
         if self._records is not None and (self._cache is None or "parameters" not in self._cache):
             return len(range(*self._rows.indices(self._records.n_rows)))
@@ -216,6 +245,14 @@ class DeviceChain(Sequence):
                     return DeviceChain(self._records, self._chain, self._model, rows=slice(r.start, r.stop, r.step))
             return DeviceChain(self.parameters[i], self.stats[i], self.accepted[i], self._model)
         theta = np.array(self.parameters[i])
-        out = self._model(theta) if self._model is not None else None
+        from .models import DeviceModel
+
+        if isinstance(self._model, DeviceModel) and self._model.reference is None:
+            # a DeviceModel without a host reference: this row on the device (with one, the host call below stays as it was)
+            dev = self._records.parameters.device.index or 0 if self._records is not None and self._records.on_device else 0
+            out = self._model.evaluate(theta[None, :], device=dev)
+            out = (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+        else:
+            out = self._model(theta) if self._model is not None else None
         out, qoi = out if isinstance(out, tuple) else (out, None)  # posterior.py:97-101
         return Link(theta, float(self.stats[i, 0]), out, float(self.stats[i, 1]), qoi)

@@ -16,18 +16,30 @@ def _attribute_rows(chain, attribute, burnin):
             return np.asarray(chain.parameters[burnin:])
         if attribute == "stats":
             return np.asarray(chain.stats[burnin:])
+        if attribute in ("model_output", "qoi") and _replays(chain._model, attribute):
+            return np.asarray(getattr(chain, attribute)[burnin:])  # one replay of the chain's rows on the device
         return np.array([getattr(chain[i], attribute) for i in range(burnin, len(chain))])
     if attribute == "stats":
         return np.array([[l.prior, l.likelihood, l.posterior] for l in chain[burnin:]])
     return np.array([getattr(l, attribute) for l in chain[burnin:]])
 
 
+def _replays(model, attribute):
+    """model outputs and quantities of interest of a DeviceModel's records come from the device (tinyda_amd/replay.py); "qoi" of
+    a model without one keeps the outcome it had (every link carries None)"""
+    from .models import DeviceModel
+
+    return isinstance(model, DeviceModel) and (attribute == "model_output" or model.n_qoi > 0)
+
+
 def _bulk_rows(chains, attribute, burnin):
     """All chains of a device result at once: when every value is a DeviceChain over the SAME device records, chain i being column
     i, the history crosses PCIe in one chunked pass (DeviceRecords.all_chains_host) instead of one strided gather per chain.
-    Returns [n_chains, rows, width] or None (anything else: chain by chain)."""
+    Model outputs and quantities of interest of a DeviceModel are replayed from the parameter records on the device, level by
+    level with that level's model, and cross the same way.  Returns [n_chains, rows, width] or None (anything else: chain by chain)."""
     first = chains[0]
-    if attribute not in ("parameters", "stats") or not isinstance(first, DeviceChain) or first._records is None or burnin < 0:
+    replayed = attribute in ("model_output", "qoi") and isinstance(first, DeviceChain) and _replays(first._model, attribute)
+    if not (attribute in ("parameters", "stats") or replayed) or not isinstance(first, DeviceChain) or first._records is None or burnin < 0:
         return None
     recs = first._records
     if recs.n_chains != len(chains):
@@ -35,6 +47,12 @@ def _bulk_rows(chains, attribute, burnin):
     for i, c in enumerate(chains):
         if not isinstance(c, DeviceChain) or c._records is not recs or c._chain != i or c._rows != slice(None):
             return None
+    if replayed:
+        if any(c._model is not first._model for c in chains):
+            return None
+        from .replay import replay_records
+
+        return replay_records(recs, first._model, (attribute,), burnin=burnin)[attribute]
     return recs.all_chains_host(attribute, start=burnin)
 
 
