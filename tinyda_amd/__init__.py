@@ -28,4 +28,5 @@ from .proposals import (  # noqa: F401
 from .records import DeviceChain  # noqa: F401
 from .api import HostFallbackWarning, release_cached_memory, sample  # noqa: F401
 from .replay import Replay, replay_records  # noqa: F401
+from .optimize import get_MAP, get_ML, maximize  # noqa: F401
 from .moments import RecursiveSampleMoments, ZeroMeanRecursiveSampleMoments  # noqa: F401

@@ -167,6 +167,40 @@ REPLAY_SYMBOLS = {
     "tda_replay_destroy": (None, [_P]),
 }
 
+
+
+class tda_optimize_problem(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dim", C.c_int32),
+        ("n_outputs", C.c_int32),
+        ("noise_kind", C.c_int32),
+        ("use_source_gradient", C.c_int32),
+        ("reserved", C.c_int32),
+        ("data", C.c_void_p),
+        ("noise", C.c_void_p),
+        ("prior_kind", C.c_void_p),
+        ("prior_loc", C.c_void_p),
+        ("prior_scale", C.c_void_p),
+    ]
+
+
+class tda_optimize_options(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_iter", C.c_int32),
+        ("gtol", C.c_double),
+        ("ftol", C.c_double),
+    ]
+
+
+# every symbol include/tinyda_amd_optimize.h declares: bound by load() only, like the replay's
+OPTIMIZE_SYMBOLS = {
+    "tda_optimizer_create": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(tda_optimize_problem), C.POINTER(_P)]),
+    "tda_optimizer_run": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(tda_optimize_options), _P, _P, _P, _P]),
+    "tda_optimizer_destroy": (None, [_P]),
+}
+
 _lib = None
 
 
@@ -208,7 +242,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # missing ROCm runtime etc.
         raise EngineError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

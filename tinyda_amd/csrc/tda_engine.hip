@@ -1379,3 +1379,4 @@ int64_t tda_release_cached_memory(void) { return (int64_t)g_pool.trim(); }
 #include "tda_host_query.inc"
 #include "tda_host_inspect.inc"
 #include "tda_host_replay.inc"
+#include "tda_host_optimize.inc"

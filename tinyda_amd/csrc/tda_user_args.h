@@ -107,3 +107,36 @@ struct UserReplayArgs {
   double* qoi;           // [R][N][nq] or null
   long long* n_eval;     // model evaluations, added to (may be null)
 };
+
+// The optimiser (tda_user_maximize): multi-start L-BFGS towards a maximum of the log-posterior (objective 0) or of the
+// log-likelihood alone (objective 1), one wave per start, every start from its initial point to its end in one launch.
+// TDA_MAP_HISTORY pairs (s, y) per start live in LDS, a ring of 2 * TDA_MAP_HISTORY * 128 doubles, beside the point and its
+// gradient (128 doubles each); a start ends with one of the status words below.
+#define TDA_MAP_HISTORY 8
+#define TDA_MAP_HALVINGS 40
+#define TDA_MAP_FLOOR 64.0  // in units of eps max(1, |f|): closer values do not tell two points apart, the line search then looks at slopes
+enum {
+  TDA_MAP_CONVERGED_GRADIENT = 0,  // max_j |g_j| <= gtol
+  TDA_MAP_CONVERGED_VALUE = 1,     // ftol > 0 and an accepted step gained <= ftol * max(1, |f|)
+  TDA_MAP_MAX_ITER = 2,
+  TDA_MAP_LINESEARCH_FAILED = 3,   // no trial of the backtracking passed, along the L-BFGS direction and along the gradient
+  TDA_MAP_INFEASIBLE_START = 4,    // f(x0) is not finite: x0 is returned
+  TDA_MAP_NONFINITE_GRADIENT = 5,
+};
+struct UserMapArgs {
+  long long N;
+  int d, m, objective, max_iter;
+  double gtol, ftol;
+  const double* x0;  // [N][d]
+  const double* data;
+  const double* w;  // as in UserStepArgs
+  double var;
+  const double* pr_mean;  // as in UserStepArgs
+  const double* pr_pinv;
+  const double* pr_lo;
+  const double* pr_hi;
+  double logconst;
+  double* x;      // [N][d]
+  double* stats;  // [N][6]: log-prior, log-likelihood, objective, max_j |g_j|, iterations, objective evaluations
+  int* status;    // [N]
+};

@@ -67,9 +67,11 @@ struct UserProgramSpec {
   bool loglike_wave = false;    // (with loglike_source) the source's tda_loglike_wave, not its tda_loglike_term
   bool replay = false;          // the replay program (tda_user_replay), not the step program: of the fields above, forward_wave alone applies
   int qoi_form = 0;             // (with replay) 0 no quantity of interest, 1 the source's tda_qoi, 2 its tda_qoi_wave
+  bool map = false;             // the optimiser (tda_user_maximize) in place of the kernels that sample: with `mala` over the source's
+                                // gradient (the MALA program's requirements), without it over differences of the step program's objective
   bool operator==(const UserProgramSpec& o) const {
     return mala == o.mala && loglike_source == o.loglike_source && prior_form == o.prior_form && forward_wave == o.forward_wave &&
-           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave && replay == o.replay && qoi_form == o.qoi_form;
+           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave && replay == o.replay && qoi_form == o.qoi_form && map == o.map;
   }
 };
 
@@ -85,6 +87,13 @@ inline size_t user_dynamic_lds(const UserProgramSpec& spec, int m) {
 
 // dynamic LDS of the replay kernel: the outputs s_out[m] (always there: the quantities read them) and behind them s_qoi[n_qoi]
 inline size_t user_replay_lds(int m, int n_qoi) { return ((size_t)m + (size_t)n_qoi) * sizeof(double); }
+
+// LDS of the optimiser, per start.  Dynamic: what the program it stands in for holds for the same source (user_dynamic_lds: the
+// MALA program's sensitivities over the source's gradient, the step program's outputs otherwise).  Static, beside what the
+// source's forms declare (parameters, s_grad, TDA_WORKSPACE): the ring of TDA_MAP_HISTORY pairs of 128 doubles, their 1 / s^T y, and
+// the point and its gradient (128 doubles each) and four scalars carried between iterations
+inline size_t user_map_dynamic_lds(const UserProgramSpec& spec, int m) { return user_dynamic_lds(spec, m); }
+constexpr size_t user_map_ring_lds() { return (2 * (size_t)TDA_MAP_HISTORY * 128 + TDA_MAP_HISTORY + 2 * 128 + 4) * sizeof(double); }
 
 // How many rows of a chain one wave of the replay walks.  A long segment evaluates the model once per accepted state (a row that
 // repeats its predecessor is copied forward, but a segment's first row is always evaluated); a short one gives the device more
@@ -121,6 +130,7 @@ std::vector<const char*> user_program_options(const UserProgramSpec& s) {
   if (s.loglike_source) opts.push_back("-DTDA_LOGLIKE_SOURCE");
   if (s.loglike_source && s.loglike_wave) opts.push_back("-DTDA_LOGLIKE_WAVE");  // (under MALA: tda_loglike_grad_wave too)
   if (s.mala) opts.push_back("-DTDA_USER_MALA");
+  if (s.map) opts.push_back("-DTDA_USER_MAP");
   if (s.prior_form) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines the prior's gradient too)
   if (s.prior_form == 2) opts.push_back("-DTDA_PRIOR_WAVE");
   if (s.forward_wave) opts.push_back("-DTDA_FORWARD_WAVE");
@@ -172,9 +182,11 @@ UserBuildError diagnose_user_build(std::string log, const UserProgramSpec& spec,
     return {TDA_ERR_UNSUPPORTED, buf};
   }
   for (const UserMissingRow& row : USER_MISSING)
-    if ((row.applies & (spec.replay ? USER_REPLAY : spec.mala ? USER_MALA : USER_STEPS)) && log.find(row.tag) != std::string::npos) return {row.code, row.message};
+    if ((row.applies & (spec.replay ? USER_REPLAY : spec.mala ? USER_MALA : USER_STEPS)) && log.find(row.tag) != std::string::npos)
+      return {row.code, std::string(spec.map && spec.mala ? "the optimiser over the source's gradient needs what MALA needs -- " : "") + row.message};
   if (log.size() > 400) log.resize(400);
-  snprintf(buf, sizeof buf, "the forward-model source does not compile%s: %s", spec.replay ? " with the replay kernel" : spec.mala ? " with the MALA kernels" : "",
+  snprintf(buf, sizeof buf, "the forward-model source does not compile%s: %s",
+           spec.replay ? " with the replay kernel" : spec.map ? (spec.mala ? " with the optimiser over its gradient" : " with the optimiser") : spec.mala ? " with the MALA kernels" : "",
            log.c_str());
   return {TDA_ERR_INVALID, buf};
 }

@@ -52,6 +52,12 @@
 //                         (converged call site, __syncthreads() legal).  qoi: LDS, n_qoi doubles, NaN before the call (an entry
 //                         left unwritten stays NaN: a NaN quantity is data, nothing is rejected here); `work` is what
 //                         tda_forward_wave left at the same theta (null without TDA_WORKSPACE)
+// and one selects the optimiser, a program of its own as well:
+//   -DTDA_USER_MAP        the optimiser kernel (tda_user_maximize) instead of the kernels that sample: multi-start L-BFGS towards a
+//                         maximum of log-prior + log-likelihood, or of the log-likelihood alone.  Together with -DTDA_USER_MALA the
+//                         gradient is the MALA kernels' (the source's vector-Jacobian product and the gradients of its likelihood
+//                         and prior, required as MALA requires them); alone it is a forward difference of the objective, d
+//                         evaluations per gradient.  The form switches apply as above
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -184,6 +190,38 @@ __device__ __forceinline__ double tda_loglike_of_sum(double sum, const double* w
 #endif
 }
 
+#ifdef TDA_USER_MAP
+// log-prior of the point (x, x2) that stands in s_th, as tda_user_steps and tda_user_mala_steps evaluate lp_n (the same
+// functions, the same summation: the same bits for the same state); the support bounds of uniform components as in tda_user_steps
+__device__ __forceinline__ double tda_map_logprior(const UserMapArgs& a, const double* s_th, int lane, double x, double x2) {
+  const int lane2 = lane + 64;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+  (void)x, (void)x2, (void)lj, (void)lj2;
+  return tda_wave_sum(tda_logprior_wave(s_th, a.d, a.pr_mean, a.pr_pinv, lane));
+#else
+  (void)s_th;
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+#ifdef TDA_PRIOR_SOURCE
+  double pj = lj ? tda_logprior_term(x, pm, pinv, lane) : 0.0;
+  if (lj2) pj += tda_logprior_term(x2, pm2, pinv2, lane2);
+  return tda_wave_sum(pj);
+#else
+  const double dv = x - pm;
+  double pj = lj ? dv * dv * pinv : 0.0;
+  if (a.pr_lo && lj && (x < a.pr_lo[lane] || x > a.pr_hi[lane])) pj = __builtin_inf();
+  if (lj2) {
+    const double dv2 = x2 - pm2;
+    pj += dv2 * dv2 * pinv2;
+    if (a.pr_lo && (x2 < a.pr_lo[lane2] || x2 > a.pr_hi[lane2])) pj = __builtin_inf();
+  }
+  return -0.5 * (a.logconst + tda_wave_sum(pj));
+#endif
+#endif
+}
+#endif
+
 #ifdef TDA_USER_REPLAY
 // Outputs and quantities of interest of recorded parameters, after the run: the forward model is deterministic, so the records
 // [R][N][d] hold everything that the reference's Link carries beside them (link.py:23-48: model_output, qoi).  One wave per
@@ -282,6 +320,13 @@ __device__ __forceinline__ double tda_loglike(const double* s_th, int lane, int 
 #endif
   return tda_loglike_of_sum(tda_wave_sum(sum), w, var);
 }
+#ifdef TDA_USER_MAP
+// the optimiser without a gradient in the source (tda_user_maximize below, in place of the three step kernels): the
+// log-likelihood is tda_loglike, the gradient a difference of objective values
+__device__ __forceinline__ double tda_map_loglike(const UserMapArgs& a, const double* s_th, double* s_out, double* s_work, int lane) {
+  return tda_loglike(s_th, lane, a.d, a.m, a.data, a.w, a.var, s_out, s_work);
+}
+#else
 extern "C" __global__ void __launch_bounds__(64) tda_user_steps(const UserStepArgs a) {
   __shared__ double s_th[128];  // (65 .. 128 parameters: a lane holds parameters `lane` and `lane + 64`)
   TDA_DECLARE_OUT;
@@ -463,6 +508,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_eval(long long N, int 
 #endif
   for (int o = lane; o < m; o += 64) F[c * m + o] = TDA_OUTPUT(o);
 }
+#endif  // TDA_USER_MAP
 
 #else  // TDA_USER_MALA
 // outputs of the model at the parameters in s_th: returns this lane's share of the sum that tda_loglike_of_sum finishes (the
@@ -531,6 +577,38 @@ __device__ __forceinline__ double tda_mala_outputs(const UserMalaArgs& a, const 
   return sum;
 }
 #endif
+#ifdef TDA_USER_MAP
+// the optimiser over the source's own gradient (tda_user_maximize below, in place of the two MALA kernels): the log-likelihood
+// as tda_user_mala_steps has its ll_n, which leaves the sensitivities in s_sens, and the gradient as it has its gp
+__device__ __forceinline__ double tda_map_loglike(const UserMapArgs& a, const double* s_th, double* s_sens, double* s_work, int lane) {
+  UserMalaArgs ma{};
+  ma.d = a.d, ma.m = a.m, ma.data = a.data, ma.w = a.w, ma.var = a.var;
+  return tda_loglike_of_sum(tda_wave_sum(tda_mala_outputs(ma, s_th, s_sens, s_work, lane)), a.w, a.var);
+}
+// gradient of the objective at the point (x, x2) whose evaluation was the last one: s_th, s_sens and the workspace still hold it
+__device__ __forceinline__ void tda_map_gradient(const UserMapArgs& a, const double* s_th, double* s_sens, double* s_grad, double* s_work, int lane, double x,
+                                                 double x2, double& g, double& g2) {
+  const int lane2 = lane + 64;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d, prior = a.objective == 0;
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+  (void)pm, (void)pinv, (void)pm2, (void)pinv2, (void)x, (void)x2;
+#ifdef TDA_GRADIENT_WAVE
+  s_grad[lane] = 0.0;
+  s_grad[lane2] = 0.0;
+  __syncthreads();  // s_sens complete
+  tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
+  __syncthreads();
+  g = lj ? (prior ? TDA_PRIOR_GRAD(x, pm, pinv, lane) : 0.0) + s_grad[lane] : 0.0;
+  g2 = lj2 ? (prior ? TDA_PRIOR_GRAD(x2, pm2, pinv2, lane2) : 0.0) + s_grad[lane2] : 0.0;
+#else
+  (void)s_grad, (void)s_work;
+  __syncthreads();  // s_sens complete
+  g = lj ? (prior ? TDA_PRIOR_GRAD(x, pm, pinv, lane) : 0.0) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+  g2 = lj2 ? (prior ? TDA_PRIOR_GRAD(x2, pm2, pinv2, lane2) : 0.0) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+#endif
+}
+#else
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
   extern __shared__ double s_sens[];  // [m] ([2 m] under TDA_LOGLIKE_WAVE: the outputs behind the sensitivities)
   __shared__ double s_th[128];
@@ -677,4 +755,218 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserM
   if (lane2 < a.DP) a.grad[row + lane2] = lj2 ? TDA_PRIOR_GRAD(th2, a.pr_mean[lane2], a.pr_pinv[lane2], lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
 #endif
 }
+#endif  // TDA_USER_MAP
 #endif  // TDA_USER_MALA
+
+#if defined(TDA_USER_MAP) && !defined(TDA_USER_REPLAY)
+// A mode of the posterior (the reference's get_MAP / get_ML, utils.py:204-269: scipy.optimize.minimize over a Python callable
+// from one start), from many starts at once: one wave per start, lane j owns parameters j and j + 64, one launch takes every
+// start from its initial point to its end.  The objective f is lp_n + ll_n of tda_user_mala_steps (objective 1: ll_n alone,
+// the prior and its support ignored), the gradient its gp -- or, without a gradient in the source, forward differences of f.
+// L-BFGS ascent: the last TDA_MAP_HISTORY pairs s = x' - x, y = g - g' in LDS (a lane reads and writes its own two entries of a
+// pair only, so the ring needs no barrier), two-loop recursion with every inner product a tda_wave_sum, initial scaling
+// s^T y / y^T y.  Without history the direction is g, scaled to unit 2-norm when |g|_2 > 1.  Backtracking Armijo from t = 1; a
+// trial whose value is NaN or -inf (outside a support) fails like any other, so iterates never leave the support.
+// Every value that a branch around a source function is taken on is the result of tda_wave_sum / tda_map_max (an xor butterfly:
+// the same bits in all 64 lanes) or a kernel argument: the wave never diverges around a call that may hold a barrier, every
+// loop has a static bound, and the wave leaves the iteration loop at its top only.
+__device__ __forceinline__ double tda_map_max(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ bool tda_map_finite(double v) { return v - v == 0.0; }
+// f at (x, x2): the point goes into s_th behind the barrier that ends the previous evaluation's reads
+__device__ __forceinline__ double tda_map_value(const UserMapArgs& a, double* s_th, double* s_buf, double* s_work, int lane, double x, double x2, double& lp,
+                                                double& ll) {
+  __syncthreads();
+  s_th[lane] = x;
+  s_th[lane + 64] = x2;
+  __syncthreads();
+  ll = tda_map_loglike(a, s_th, s_buf, s_work, lane);
+  lp = tda_map_logprior(a, s_th, lane, x, x2);
+  return a.objective == 0 ? lp + ll : ll;
+}
+#ifndef TDA_USER_MALA
+// forward differences of f at (x, x2), where f = f0: h_j = 2^-26 max(1, |x_j|) (scipy's step for the reference's call), the
+// backward difference where the forward point is not finite; false when neither is.  d evaluations by the wave, one after the other.
+__device__ __forceinline__ bool tda_map_difference(const UserMapArgs& a, double* s_th, double* s_buf, double* s_work, int lane, double x, double x2, double f0,
+                                                   double& g, double& g2, int& neval) {
+  bool ok = true;
+  g = 0.0, g2 = 0.0;
+  for (int j = 0; j < a.d; ++j) {
+    const double xj = __shfl(j < 64 ? x : x2, j & 63);
+    const double hj = (xj + 0x1p-26 * fmax(1.0, fabs(xj))) - xj;  // (the step that the addition really takes)
+    const bool mine = lane == (j & 63);
+    double lp, ll;
+    double fj = tda_map_value(a, s_th, s_buf, s_work, lane, mine && j < 64 ? x + hj : x, mine && j >= 64 ? x2 + hj : x2, lp, ll);
+    double gj = (fj - f0) / hj;
+    ++neval;
+    if (!tda_map_finite(fj)) {
+      fj = tda_map_value(a, s_th, s_buf, s_work, lane, mine && j < 64 ? x - hj : x, mine && j >= 64 ? x2 - hj : x2, lp, ll);
+      gj = (f0 - fj) / hj;
+      ++neval;
+      ok = ok && tda_map_finite(fj);
+    }
+    if (mine && j < 64) g = gj;
+    if (mine && j >= 64) g2 = gj;
+  }
+  return ok;
+}
+#endif
+extern "C" __global__ void __launch_bounds__(64) tda_user_maximize(const UserMapArgs a) {
+#ifdef TDA_USER_MALA
+  extern __shared__ double s_buf[];  // s_sens[m] ([2 m] under TDA_LOGLIKE_WAVE), as in tda_user_mala_steps
+#else
+  TDA_DECLARE_OUT;
+  double* const s_buf = s_out;
+#endif
+  __shared__ double s_th[128];
+  TDA_DECLARE_WORK;
+#if defined(TDA_USER_MALA) && defined(TDA_GRADIENT_WAVE)
+  __shared__ double s_grad[128];
+#else
+  double* const s_grad = nullptr;
+#endif
+  __shared__ double s_S[TDA_MAP_HISTORY][128], s_Y[TDA_MAP_HISTORY][128];  // the ring of pairs
+  __shared__ double s_rho[TDA_MAP_HISTORY];                                 // 1 / s^T y of a pair (every lane writes the same bits)
+  __shared__ double s_x[128], s_g[128];  // the point and its gradient, a lane's own two entries: not in registers across the source's functions
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  // log-prior and log-likelihood of the point, the scaling s^T y / y^T y and the last gain: carried from iteration to iteration
+  // and read a few times in each, so they live in LDS too (every lane writes the same bits and reads its own write back)
+  __shared__ double s_stat[4];
+  double f = 0.0, gmax = __builtin_nan("");
+  s_stat[0] = 0.0, s_stat[1] = 0.0, s_stat[2] = 1.0, s_stat[3] = 0.0;
+  int neval = 0, iters = 0, status = -1, count = 0, head = 0;
+  s_x[lane] = lj ? a.x0[c * a.d + lane] : 0.0, s_x[lane2] = lj2 ? a.x0[c * a.d + lane2] : 0.0;
+  s_g[lane] = 0.0, s_g[lane2] = 0.0;
+  // Pass -1 evaluates the start, as the one "trial" of a search with the zero direction that a finite value accepts: the
+  // source's functions are inlined at one place for the objective and one for the gradient, whatever point they are called at.
+  for (int it = -1; it <= a.max_iter; ++it) {
+    const bool first = it < 0;
+    if (status >= 0) break;
+    if (!first && gmax <= a.gtol) {
+      status = TDA_MAP_CONVERGED_GRADIENT;
+      break;
+    }
+    if (it > 0 && a.ftol > 0.0 && s_stat[3] <= a.ftol * fmax(1.0, fabs(f))) {
+      status = TDA_MAP_CONVERGED_VALUE;
+      break;
+    }
+    if (it == a.max_iter) {
+      status = TDA_MAP_MAX_ITER;
+      break;
+    }
+    // the direction: two-loop recursion over the pairs, newest first
+    double p = s_g[lane], p2 = s_g[lane2], al[TDA_MAP_HISTORY];
+#pragma unroll
+    for (int k = 0; k < TDA_MAP_HISTORY; ++k) {
+      al[k] = 0.0;
+      if (k < count) {
+        const int slot = (head - 1 - k) & (TDA_MAP_HISTORY - 1);
+        al[k] = s_rho[slot] * tda_wave_sum(s_S[slot][lane] * p + s_S[slot][lane2] * p2);
+        p -= al[k] * s_Y[slot][lane];
+        p2 -= al[k] * s_Y[slot][lane2];
+      }
+    }
+    if (count > 0) {
+      p *= s_stat[2];
+      p2 *= s_stat[2];
+    }
+#pragma unroll
+    for (int k = TDA_MAP_HISTORY - 1; k >= 0; --k) {
+      if (k < count) {
+        const int slot = (head - 1 - k) & (TDA_MAP_HISTORY - 1);
+        const double beta = s_rho[slot] * tda_wave_sum(s_Y[slot][lane] * p + s_Y[slot][lane2] * p2);
+        p += s_S[slot][lane] * (al[k] - beta);
+        p2 += s_S[slot][lane2] * (al[k] - beta);
+      }
+    }
+    double gtp = tda_wave_sum(s_g[lane] * p + s_g[lane2] * p2);
+    if (count > 0 && !(gtp > 0.0 && tda_map_finite(gtp))) count = 0;  // not an ascent direction: the history is dropped
+    // backtracking Armijo, along the L-BFGS direction and, when every trial there failed, once more along the gradient
+    // Where the values no longer tell the points apart (|f' - f| <= TDA_MAP_FLOOR eps max(1, |f|): the gain of a good step near a
+    // maximum, g^T H^-1 g / 2, drops below the rounding of f long before the gradient is small) the trial is judged by its
+    // slope p^T g' instead, the approximate Wolfe conditions of Hager and Zhang (2005): -(1 - 2 c1) g^T p <= p^T g' <= 0.9 g^T p.
+    bool accepted = false, okn = true;
+    double xn = 0.0, xn2 = 0.0, fn = f, lpn = 0.0, lln = 0.0, gn = 0.0, gn2 = 0.0;
+    for (int attempt = 0; attempt < 2 && !accepted; ++attempt) {
+      if (attempt == 1) {
+        if (count == 0) break;  // (the first attempt already went along the gradient)
+        count = 0;
+      }
+      if (count == 0) {  // (the start's pass: g = 0, the zero direction)
+        const double g = s_g[lane], g2 = s_g[lane2];
+        const double gg = tda_wave_sum(g * g + g2 * g2), scale = gg > 1.0 ? 1.0 / sqrt(gg) : 1.0;
+        p = g * scale, p2 = g2 * scale;
+        gtp = gg * scale;
+      }
+      double t = 1.0;
+      for (int k = 0; k <= TDA_MAP_HALVINGS; ++k) {
+        xn = s_x[lane] + t * p, xn2 = s_x[lane2] + t * p2;
+        fn = tda_map_value(a, s_th, s_buf, s_work, lane, xn, xn2, lpn, lln);
+        ++neval;
+        const bool armijo = tda_map_finite(fn) && (first || fn >= f + 1e-4 * t * gtp);
+        if (armijo || (tda_map_finite(fn) && fabs(fn - f) <= TDA_MAP_FLOOR * 0x1p-52 * fmax(1.0, fabs(f)))) {
+          // the gradient at the trial, the last point evaluated: of an accepted trial it is the next iteration's
+#ifdef TDA_USER_MALA
+          tda_map_gradient(a, s_th, s_buf, s_grad, s_work, lane, xn, xn2, gn, gn2);
+#else
+          okn = tda_map_difference(a, s_th, s_buf, s_work, lane, xn, xn2, fn, gn, gn2, neval);
+#endif
+          const double slope = tda_wave_sum(gn * p + gn2 * p2);
+          if (armijo || (okn && slope >= -(1.0 - 2e-4) * gtp && slope <= 0.9 * gtp)) {
+            accepted = true;
+            break;
+          }
+        }
+        if (first) break;
+        t *= 0.5;
+      }
+    }
+    if (first) {  // the start: its value, and where that is finite its gradient
+      f = fn, s_stat[0] = lpn, s_stat[1] = lln;
+      if (!accepted) {
+        status = TDA_MAP_INFEASIBLE_START;
+        continue;
+      }
+      s_g[lane] = gn, s_g[lane2] = gn2;
+      gmax = tda_map_max(fmax(fabs(gn), fabs(gn2)));
+      if (!okn || tda_wave_sum(tda_map_finite(gn) && tda_map_finite(gn2) ? 0.0 : 1.0) != 0.0) status = TDA_MAP_NONFINITE_GRADIENT;
+      continue;
+    }
+    if (!accepted) {
+      status = TDA_MAP_LINESEARCH_FAILED;
+      continue;
+    }
+    const bool ok = okn;
+    const double sx = xn - s_x[lane], sx2 = xn2 - s_x[lane2], yg = s_g[lane] - gn, yg2 = s_g[lane2] - gn2;
+    const double sy = tda_wave_sum(sx * yg + sx2 * yg2), yy = tda_wave_sum(yg * yg + yg2 * yg2);
+    s_stat[3] = fn - f;
+    s_x[lane] = xn, s_x[lane2] = xn2, f = fn, s_stat[0] = lpn, s_stat[1] = lln, s_g[lane] = gn, s_g[lane2] = gn2;
+    ++iters;
+    gmax = tda_map_max(fmax(fabs(gn), fabs(gn2)));
+    if (!ok || tda_wave_sum(tda_map_finite(gn) && tda_map_finite(gn2) ? 0.0 : 1.0) != 0.0) {
+      status = TDA_MAP_NONFINITE_GRADIENT;
+      continue;
+    }
+    if (sy > 0x1p-52 * yy) {  // curvature along the step: the pair enters the ring
+      s_S[head][lane] = sx, s_S[head][lane2] = sx2;
+      s_Y[head][lane] = yg, s_Y[head][lane2] = yg2;
+      s_rho[head] = 1.0 / sy;
+      s_stat[2] = sy / yy;
+      head = (head + 1) & (TDA_MAP_HISTORY - 1);
+      count = count < TDA_MAP_HISTORY ? count + 1 : TDA_MAP_HISTORY;
+    }
+  }
+  if (lj) a.x[c * a.d + lane] = s_x[lane];
+  if (lj2) a.x[c * a.d + lane2] = s_x[lane2];
+  if (lane == 0) {
+    double* st = a.stats + c * 6;
+    st[0] = s_stat[0], st[1] = s_stat[1], st[2] = f, st[3] = gmax, st[4] = (double)iters, st[5] = (double)neval;
+    a.status[c] = status;
+  }
+}
+#endif  // TDA_USER_MAP

@@ -26,10 +26,10 @@ extern "C" const char tda_user_args_text[] __attribute__((visibility("hidden")))
 namespace {
 
 // one compiled program of a level: the step program (steps, eval, level) or the MALA program (steps, grad0); or, of no level
-// and no engine, the replay program (replay: tda_host_replay.inc)
+// and no engine, the replay program (replay: tda_host_replay.inc) or the optimiser (maximize: tda_host_optimize.inc)
 struct UserProgram {
   hipModule_t mod = nullptr;
-  hipFunction_t steps = nullptr, eval = nullptr, level = nullptr, grad0 = nullptr, replay = nullptr;
+  hipFunction_t steps = nullptr, eval = nullptr, level = nullptr, grad0 = nullptr, replay = nullptr, maximize = nullptr;
   size_t out_lds = 0;    // dynamic LDS of steps / eval / level: the outputs s_out[m] of a wave-form model or likelihood (0 without one;
                          // tda_user_eval reads it under a wave-form model only and is launched with it all the same: one size per program)
   UserProgramSpec spec;  // what it was compiled with (ensure_user_program of tda_engine.hip builds it again when that changed since)
@@ -51,7 +51,7 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
   const char* const headers[] = {source, tda_user_args_text};
   const char* const names[] = {"tda_user_source.h", "tda_user_args.h"};
   hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, tda_user_program_text, spec.replay ? "tda_user_replay.hip" : mala ? "tda_user_mala.hip" : "tda_user_model.hip", 2, headers, names) != HIPRTC_SUCCESS)
+  if (hiprtcCreateProgram(&prog, tda_user_program_text, spec.replay ? "tda_user_replay.hip" : spec.map ? "tda_user_map.hip" : mala ? "tda_user_mala.hip" : "tda_user_model.hip", 2, headers, names) != HIPRTC_SUCCESS)
     return fail(TDA_ERR_HIP, "hiprtcCreateProgram failed");
   std::vector<const char*> opts = user_program_options(spec);
   if (hiprtcCompileProgram(prog, (int)opts.size(), opts.data()) != HIPRTC_SUCCESS) {
@@ -81,6 +81,21 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
       return fail(TDA_ERR_UNSUPPORTED, "the replay of a source-defined model holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters and "
                                        "TDA_WORKSPACE) + %zu bytes for its %d outputs and its %d quantities of interest (%zu of them for the quantities)",
                   stat, dyn, m, n_qoi, (size_t)n_qoi * sizeof(double));
+    }
+    return TDA_OK;
+  }
+  if (spec.map) {  // the optimiser: the LDS of the program it stands in for, and the ring of pairs in its static part
+    HIP_TRY(hipModuleGetFunction(&out->maximize, out->mod, "tda_user_maximize"));
+    out->spec = spec;
+    out->out_lds = user_map_dynamic_lds(spec, m);
+    int stat = 0;
+    HIP_TRY(hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, out->maximize));
+    if ((size_t)stat + out->out_lds > USER_LDS_MAX) {
+      const size_t dyn = out->out_lds;
+      out->unload();
+      return fail(TDA_ERR_UNSUPPORTED, "the optimiser of a source-defined model holds at most 64 KiB of LDS per start: this source needs %d bytes (parameters, "
+                                       "gradient, TDA_WORKSPACE and %zu bytes for the ring of %d L-BFGS pairs, the point, its gradient and four scalars) + %zu bytes for its %d outputs",
+                  stat, user_map_ring_lds(), (int)TDA_MAP_HISTORY, dyn, m);
     }
     return TDA_OK;
   }
