@@ -16,6 +16,7 @@ NOISE_SOURCE = 4  # a separable log-likelihood in the level's HIP source (likeli
 PRIOR_NORMAL, PRIOR_UNIFORM, PRIOR_SOURCE = 0, 1, 2  # kinds of set_prior_joint; 2: tda_logprior_term in the levels' HIP source (likelihoods.DevicePrior)
 AEM_NONE, AEM_STATE_INDEPENDENT, AEM_STATE_DEPENDENT, AEM_STATE_INDEPENDENT_DIAGONAL = 0, 1, 2, 3
 PROP_GRW, PROP_PCN, PROP_AM, PROP_DREAMZ, PROP_INDEPENDENCE, PROP_OWCN, PROP_MALA = 0, 1, 2, 3, 4, 5, 6
+PROP_HMC = 7  # Hamiltonian Monte Carlo over a source-defined model (proposals.HMC; include/tinyda_amd_hmc.h)
 
 
 class EngineError(RuntimeError):
@@ -201,6 +202,11 @@ OPTIMIZE_SYMBOLS = {
     "tda_optimizer_destroy": (None, [_P]),
 }
 
+# every symbol include/tinyda_amd_hmc.h declares: bound by load() only (the CPU build of the ABI has no HMC)
+HMC_SYMBOLS = {
+    "tda_engine_set_hmc": (C.c_int, [_P, C.c_int32, _P]),
+}
+
 _lib = None
 
 
@@ -242,7 +248,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # missing ROCm runtime etc.
         raise EngineError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -301,7 +301,7 @@ struct Level {
   UserProgram uprog;       // tda_user_steps / tda_user_eval / tda_user_level_action
   std::string usrc;        // the model source (the programs are compiled from it: ensure_user_program)
   UserForms forms;         // the optional functions of the contract that usrc defines
-  UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0 (built at init only when the proposal is MALA)
+  UserProgram uprog_mala;  // tda_user_mala_steps / tda_user_mala_grad0 (built at init only when the proposal is MALA; under HMC: tda_user_hmc_steps in place of the first)
   DevBuf<double> udata, uw;
   DevBuf<double> upar;  // TDA_NOISE_SOURCE: the per-output parameters of the source's tda_loglike_term (as given, not inverted)
   double ros_a = 1.0, ros_b = 10.0, ros_data = 0.0;
@@ -357,6 +357,11 @@ struct tda_engine {
   std::vector<double> ow_V_h, ow_lam_h;        // V [d][d] row-major (columns = eigenvectors), lambda [d]
   DevBuf<double> ow_VVt, ow_lam;               // [2][DP][DP]: V, then V^T; [DP]
   DevBuf<double> mala_H, mala_c, mala_grad;    // MALA: H [DP][DP] (symmetric), c [DP], grad log post of the current states [NP][DP]
+  // HMC (TDA_PROP_HMC, tda_engine_set_hmc): leapfrog steps per proposal and the diagonal inverse mass (configuration, not chain
+  // state: the state is MALA's, mala_grad included)
+  int hmc_n_leapfrog = 8;
+  std::vector<double> hmc_inv_mass_h;  // [d]; empty: unit mass
+  DevBuf<double> hmc_inv_mass;         // [DP], ones in the padding (uploaded by tda_engine_init)
   DevBuf<double> q_mean_d, lq, qzblk, qzblk2[2];
   double am_sd = 1.0;
   bool L_shared = true;
@@ -1010,6 +1015,18 @@ int fill_user_mala_args(tda_engine* e, const Level& lv, UserMalaArgs& ga) {
   return TDA_OK;
 }
 
+// HMC over a source-defined model: MALA's arguments and the trajectory's configuration
+int fill_user_hmc_args(tda_engine* e, const Level& lv, UserHmcArgs& ha) {
+  if (int rc = fill_user_mala_args(e, lv, ha)) return rc;
+  ha.n_leapfrog = e->hmc_n_leapfrog;
+  ha.inv_mass = e->hmc_inv_mass.p;
+  return TDA_OK;
+}
+
+// the proposals that run on the gradient of the log-posterior: MALA, and HMC (source-defined models only: tda_engine_init
+// refuses it over anything else, so that every branch below that HMC shares with MALA is the source-defined one)
+inline bool gradient_proposal(int kind) { return kind == TDA_PROP_MALA || kind == TDA_PROP_HMC; }
+
 constexpr int MODEL_CALLBACK = 3;
 
 void fill_ext_args(tda_engine* e, const Level& lv, ExtArgs& xa) {
@@ -1121,6 +1138,7 @@ UserProgramSpec user_program_spec(const tda_engine* e, const Level& lv, bool mal
   s.prior_form = !e->prior_source ? 0 : lv.forms.prior_wave ? 2 : 1;
   s.forward_wave = lv.forms.forward_wave;
   s.gradient_wave = mala && lv.forms.gradient_wave;
+  s.hmc = mala && e->pp.kind == TDA_PROP_HMC;
   return s;
 }
 
@@ -1380,3 +1398,4 @@ int64_t tda_release_cached_memory(void) { return (int64_t)g_pool.trim(); }
 #include "tda_host_inspect.inc"
 #include "tda_host_replay.inc"
 #include "tda_host_optimize.inc"
+#include "tda_host_hmc.inc"

@@ -17,10 +17,11 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     if (e->is_dreamz) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under DREAM(Z) is not lowered");
     if (e->pp.kind == TDA_PROP_PCN || e->pp.kind == TDA_PROP_OWCN)
       return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under pCN and operator-weighted pCN is not lowered (they need a Gaussian prior)");
-    if (e->pp.kind == TDA_PROP_MALA) {  // tda_user_mala_steps takes the prior's own gradient from the level's source (single level: set_proposal)
+    if (gradient_proposal(e->pp.kind)) {  // tda_user_mala_steps / tda_user_hmc_steps take the prior's own gradient from the level's source (single level: set_proposal)
       const UserForms& f0 = e->levels[0].forms;
       if (f0.prior_wave ? !f0.prior_grad : !f0.prior_term_grad)
-        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under MALA needs %s in the level's source", f0.prior_wave ? TDA_SIG_LOGPRIOR_GRAD : TDA_SIG_LOGPRIOR_TERM_GRAD);
+        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under %s needs %s in the level's source", e->pp.kind == TDA_PROP_HMC ? "HMC" : "MALA",
+                    f0.prior_wave ? TDA_SIG_LOGPRIOR_GRAD : TDA_SIG_LOGPRIOR_TERM_GRAD);
     }
     if (e->pp.kind == TDA_PROP_INDEPENDENCE) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under the Independence proposal is not lowered");
     if (e->aem) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior together with an error model is not lowered");
@@ -35,9 +36,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "a dense observation covariance in a hierarchy: at most %d levels", (int)AEM_MAXLEV);
   }
   if (e->wide) {  // 65 .. 128 parameters (tda_kernels_wide.h): what that path is built for
-    const bool user_mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA && e->nlev == 1 && e->levels[0].model == MODEL_USER;
+    const bool user_mala = !e->is_dreamz && gradient_proposal(e->pp.kind) && e->nlev == 1 && e->levels[0].model == MODEL_USER;
     if (e->is_dreamz || (e->pp.kind != TDA_PROP_GRW && e->pp.kind != TDA_PROP_PCN && e->pp.kind != TDA_PROP_AM && !user_mala))
-      return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: GaussianRandomWalk, CrankNicolson and AdaptiveMetropolis are lowered (MALA: single-level source-defined models)");
+      return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: GaussianRandomWalk, CrankNicolson and AdaptiveMetropolis are lowered (MALA and HMC: single-level source-defined models)");
     if (e->pp.kind == TDA_PROP_AM && e->pp.block_moments) return fail(TDA_ERR_UNSUPPORTED, "more than 64 parameters: block_moments is not lowered");
     for (const Level& l0 : e->levels) {
       // (a batched host callback, single level or in a host-sequenced hierarchy: k_ext_propose / k_ext_accept / k_ext_level_action take a
@@ -61,17 +62,21 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       return fail(TDA_ERR_UNSUPPORTED, "operator-weighted pCN is lowered for linear, callback and source-defined forward models");
     if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "operator-weighted pCN needs a Gaussian prior");
   }
-  if (e->prop_set && !e->is_dreamz && e->pp.kind == TDA_PROP_MALA) {
+  if (e->prop_set && !e->is_dreamz && gradient_proposal(e->pp.kind)) {
     const Level& l0 = e->levels[0];
+    const bool hmc = e->pp.kind == TDA_PROP_HMC;
+    const char* const gname = hmc ? "HMC" : "MALA";
+    if (hmc && l0.model != MODEL_USER)  // (k_mh_steps has MALA's closed-form gradient of the linear model and no leapfrog loop)
+      return fail(TDA_ERR_UNSUPPORTED, "HMC is lowered for source-defined forward models with tda_gradient only (the built-in linear model has MALA)");
     if (l0.model != MODEL_LINEAR && l0.model != MODEL_USER)
       return fail(TDA_ERR_UNSUPPORTED, "MALA is lowered for linear and source-defined forward models only (exact gradient)");
-    if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "MALA needs a Gaussian prior");
-    if (l0.noise_kind == TDA_NOISE_ADAPTIVE) return fail(TDA_ERR_UNSUPPORTED, "MALA: adaptive likelihoods are not lowered");
-    if (l0.model == MODEL_USER) {  // tda_user_mala_steps: iso / diag noise, diagonal Gaussian or source-defined prior, sensitivity of m <= 2048 outputs in LDS
+    if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "%s needs a Gaussian prior", gname);
+    if (l0.noise_kind == TDA_NOISE_ADAPTIVE) return fail(TDA_ERR_UNSUPPORTED, "%s: adaptive likelihoods are not lowered", gname);
+    if (l0.model == MODEL_USER) {  // tda_user_mala_steps / tda_user_hmc_steps: iso / diag noise, diagonal Gaussian or source-defined prior, sensitivity of m <= 2048 outputs in LDS
       if ((e->prior_joint && !e->prior_source) || e->prior_kind == PRIOR_DENSE)
-        return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model needs a multivariate normal prior with diagonal covariance or a source-defined prior");
-      if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: isotropic or diagonal noise");
-      if (l0.m > 2048) return fail(TDA_ERR_UNSUPPORTED, "MALA over a source-defined model: at most 2048 outputs");
+        return fail(TDA_ERR_UNSUPPORTED, "%s over a source-defined model needs a multivariate normal prior with diagonal covariance or a source-defined prior", gname);
+      if (l0.noise_kind == TDA_NOISE_DENSE) return fail(TDA_ERR_UNSUPPORTED, "%s over a source-defined model: isotropic or diagonal noise", gname);
+      if (l0.m > 2048) return fail(TDA_ERR_UNSUPPORTED, "%s over a source-defined model: at most 2048 outputs", gname);
     }
   }
   for (const Level& ls : e->levels) {
@@ -265,9 +270,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->nlev == 1) return TDA_OK;
   }
-  const bool owcn = !e->is_dreamz && e->pp.kind == TDA_PROP_OWCN, mala = !e->is_dreamz && e->pp.kind == TDA_PROP_MALA;
-  const bool user_mala = mala && e->levels[0].model == MODEL_USER;
-  // the second program: GRW / pCN / AM engines never build it
+  const bool owcn = !e->is_dreamz && e->pp.kind == TDA_PROP_OWCN, mala = !e->is_dreamz && gradient_proposal(e->pp.kind);
+  const bool user_mala = mala && e->levels[0].model == MODEL_USER;  // (HMC: always, the refusals above)
+  // the second program (the MALA program, or under HMC the HMC program): GRW / pCN / AM engines never build it
   if (user_mala && (rc = ensure_user_program(e, e->levels[0], true))) return rc;
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;
@@ -283,6 +288,11 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     // source-defined model: the gradient comes from the model's own tda_gradient at every step (tda_user_mala_steps)
     if ((rc = e->mala_grad.alloc((size_t)NP * DP))) return rc;
     HIP_TRY(hipMemsetAsync(e->mala_grad.p, 0, (size_t)NP * DP * sizeof(double), e->stream));
+    if (e->pp.kind == TDA_PROP_HMC) {  // the diagonal inverse mass, ones in the padding (and everywhere without tda_engine_set_hmc's array)
+      std::vector<double> wm(DP, 1.0);
+      for (int j = 0; j < d && !e->hmc_inv_mass_h.empty(); ++j) wm[j] = e->hmc_inv_mass_h[j];
+      if ((rc = e->hmc_inv_mass.upload(wm))) return rc;
+    }
   } else if (mala) {
     // linear model: gradient of the log-posterior of the linear-Gaussian target (proposal.py:986-998; utils.py:273-287) in
     // closed form, grad = c - H theta with

@@ -232,10 +232,11 @@ int tda_engine_set_level(tda_engine* e, int level, int m, const double* A, const
 int tda_engine_set_proposal(tda_engine* e, const tda_proposal_params* p) {
   if (!e || !p) return fail(TDA_ERR_INVALID, "null argument");
   if (p->struct_size != sizeof(tda_proposal_params)) return fail(TDA_ERR_INVALID, "tda_proposal_params.struct_size mismatch");
-  const bool indep = p->kind == TDA_PROP_INDEPENDENCE, owcn = p->kind == TDA_PROP_OWCN, mala = p->kind == TDA_PROP_MALA;
+  const bool indep = p->kind == TDA_PROP_INDEPENDENCE, owcn = p->kind == TDA_PROP_OWCN, mala = gradient_proposal(p->kind);
+  const char* const gname = p->kind == TDA_PROP_HMC ? "HMC" : "MALA";
   if ((p->kind < TDA_PROP_GRW || p->kind > TDA_PROP_AM) && !indep && !owcn && !mala) return fail(TDA_ERR_UNSUPPORTED, "proposal kind %d", p->kind);
-  if (mala && e->nlev != 1) return fail(TDA_ERR_UNSUPPORTED, "MALA is lowered for single-level chains only");
-  if (mala && !(p->scaling > 0.0)) return fail(TDA_ERR_INVALID, "MALA: scaling must be positive");
+  if (mala && e->nlev != 1) return fail(TDA_ERR_UNSUPPORTED, "%s is lowered for single-level chains only", gname);
+  if (mala && !(p->scaling > 0.0)) return fail(TDA_ERR_INVALID, "%s: scaling must be positive", gname);
   if (owcn && e->nlev != 1) return fail(TDA_ERR_UNSUPPORTED, "the operator-weighted pCN proposal is lowered for single-level chains only");
   if ((p->kind == TDA_PROP_GRW || p->kind == TDA_PROP_AM || indep) && !p->C) return fail(TDA_ERR_INVALID, "proposal covariance missing");
   if (indep && !p->q_mean) return fail(TDA_ERR_INVALID, "independence sampler: q_mean missing");
@@ -256,6 +257,10 @@ int tda_engine_set_proposal(tda_engine* e, const tda_proposal_params* p) {
     e->pp.adaptive = 0;
     e->pp.scaling = 1.0;
     e->q_mean_h.assign(p->q_mean, p->q_mean + e->d);
+  }
+  if (p->kind == TDA_PROP_HMC) {  // the defaults of tda_engine_set_hmc, which follows
+    e->hmc_n_leapfrog = 8;
+    e->hmc_inv_mass_h.clear();
   }
   if (p->C) e->prop_C_h.assign(p->C, p->C + (size_t)e->d * e->d);
   e->pp.C = nullptr;

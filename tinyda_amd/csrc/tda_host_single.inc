@@ -354,6 +354,18 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
         int xrc = ext_step(e, lv, xa);
         if (xrc) return xrc;
       }
+    } else if (lv.model == MODEL_USER && e->pp.kind == TDA_PROP_HMC) {  // (the HMC program stands in the MALA program's place: ensure_user_program)
+      UserHmcArgs ha{};
+      int urc = fill_user_hmc_args(e, lv, ha);
+      if (urc) return urc;
+      ha.S = (int)S;
+      ha.inc = sa.inc;
+      ha.u = sa.u;
+      ha.rec_params = sa.rec_params;
+      ha.rec_stats = sa.rec_stats;
+      ha.rec_acc = sa.rec_acc;
+      ScopedTimer tm(e, 1);
+      if ((urc = launch_user(lv.uprog_mala.steps, ha, user_mala_lds(lv.uprog_mala.spec, ha.m), e->stream))) return urc;
     } else if (lv.model == MODEL_USER && e->pp.kind == TDA_PROP_MALA) {
       UserMalaArgs ga{};
       int urc = fill_user_mala_args(e, lv, ga);
@@ -407,7 +419,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
       aa.period = period;
       aa.gamma_pow = std::pow(e->pp.gamma, -(double)e->k_adapt);
       aa.sd = e->am_sd;
-      aa.alpha_star = e->pp.kind == TDA_PROP_MALA ? 0.57 : 0.24;  // proposal.py:899 / :169
+      aa.alpha_star = e->pp.kind == TDA_PROP_HMC ? 0.65 : e->pp.kind == TDA_PROP_MALA ? 0.57 : 0.24;  // HMC (an extension) / proposal.py:899 / :169
       aa.eps = e->pp.epsilon;
       aa.rec_params = sa.rec_params;
       aa.am_mu = e->am_mu.p;

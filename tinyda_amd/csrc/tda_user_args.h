@@ -97,6 +97,13 @@ struct UserMalaArgs {
   unsigned char* rec_acc;
 };
 
+// HMC over a source-defined model (tda_user_hmc_steps): MALA's chain state, variates and records, and the trajectory's
+// configuration behind them.  `scaling` is the leapfrog step size.
+struct UserHmcArgs : UserMalaArgs {
+  int n_leapfrog;          // leapfrog steps per proposal, >= 1
+  const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding
+};
+
 // The replay of recorded parameters through the model (tda_user_replay): outputs and quantities of interest of the rows
 // [0, R) of N chains, one wave per chain and segment of `seg` rows.  Either destination may be null.
 struct UserReplayArgs {

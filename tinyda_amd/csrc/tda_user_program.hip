@@ -58,6 +58,10 @@
 //                         gradient is the MALA kernels' (the source's vector-Jacobian product and the gradients of its likelihood
 //                         and prior, required as MALA requires them); alone it is a forward difference of the objective, d
 //                         evaluations per gradient.  The form switches apply as above
+// and one turns the MALA program into the HMC program:
+//   -DTDA_USER_HMC        (in addition to -DTDA_USER_MALA) the HMC kernel (tda_user_hmc_steps) in place of tda_user_mala_steps:
+//                         leapfrog trajectories on the log-posterior and gradient of the MALA program, whose requirements are its own;
+//                         tda_user_mala_grad0 stays and initialises the gradient
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -609,6 +613,137 @@ __device__ __forceinline__ void tda_map_gradient(const UserMapArgs& a, const dou
 #endif
 }
 #else
+#ifdef TDA_USER_HMC
+// Hamiltonian Monte Carlo in place of tda_user_mala_steps: per step one momentum from the step's unit normals, n_leapfrog
+// leapfrog steps of size scaling[c] under the diagonal inverse mass w on the log-posterior and gradient that MALA evaluates
+// (the same calls in the same order: tda_mala_outputs, the prior's three forms, tda_gradient / tda_gradient_wave), one accept
+// test on the energy difference at the end.  The state, the momentum and the gradient stay in registers; s_th holds the moving
+// position.  The interior leapfrog steps read no variates and write no records.
+// A position whose log-posterior is not finite (outside a support, a NaN output) ends the trajectory and rejects.  That test
+// is on wave sums, the same bits in all 64 lanes, and goes through a scalar register: the wave leaves the loop as one, so every
+// source function that may hold a barrier or a shuffle is called from a converged wave.
+// Barriers: the one at the top of a leapfrog step puts the readers of s_th / s_sens / s_grad of the step before it (and of the
+// previous trajectory, whichever way it left the loop) behind it before the next position is stored.
+extern "C" __global__ void __launch_bounds__(64) tda_user_hmc_steps(const UserHmcArgs a) {
+  extern __shared__ double s_sens[];  // [m] ([2 m] under TDA_LOGLIKE_WAVE: the outputs behind the sensitivities)
+  __shared__ double s_th[128];
+  TDA_DECLARE_WORK;
+#ifdef TDA_GRADIENT_WAVE
+  __shared__ double s_grad[128];  // J^T sens at the moving position, all parameters from one tda_gradient_wave call
+#endif
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const size_t row = (size_t)c * a.DP;
+  double cur = lj ? a.theta[row + lane] : 0.0, cur2 = lj2 ? a.theta[row + lane2] : 0.0;
+  double gc = lj ? a.grad[row + lane] : 0.0, gc2 = lj2 ? a.grad[row + lane2] : 0.0;  // gradient at the current state
+  double lp = a.lp[c], ll = a.ll[c];
+  const double eps = a.scaling[c], he = 0.5 * eps;
+  const double w = lj ? a.inv_mass[lane] : 1.0, w2 = lj2 ? a.inv_mass[lane2] : 1.0;
+  const double sw = sqrt(w), sw2 = sqrt(w2);
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+  (void)pm, (void)pinv, (void)pm2, (void)pinv2;
+  int nacc = 0;
+  for (int s = 0; s < a.S; ++s) {
+    const double* z = a.inc + ((size_t)s * a.NP + c) * a.DP;
+    double p = lj ? z[lane] / sw : 0.0, p2 = lj2 ? z[lane2] / sw2 : 0.0;  // momentum ~ N(0, 1 / w)
+    const double k0 = 0.5 * tda_wave_sum(w * (p * p) + w2 * (p2 * p2));
+    p += he * gc;
+    p2 += he * gc2;
+    double th = cur, th2 = cur2, g = gc, g2 = gc2, lp_n = lp, ll_n = ll, post_n = lp + ll;
+    int alive = 1;
+    for (int i = 1; i <= a.n_leapfrog; ++i) {
+      th += eps * (w * p);  // (a lane without a parameter keeps p = 0 and th = 0)
+      th2 += eps * (w2 * p2);
+      __syncthreads();
+      s_th[lane] = th;
+      s_th[lane2] = th2;
+      __syncthreads();
+      const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, s_work, lane));
+      ll_n = tda_loglike_of_sum(sum, a.w, a.var);
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+      lp_n = tda_wave_sum(tda_logprior_wave(s_th, a.d, a.pr_mean, a.pr_pinv, lane));
+#elif defined(TDA_PRIOR_SOURCE)
+      double pj = lj ? tda_logprior_term(th, pm, pinv, lane) : 0.0;
+      if (lj2) pj += tda_logprior_term(th2, pm2, pinv2, lane2);
+      lp_n = tda_wave_sum(pj);
+#else
+      double pj = 0.0;
+      if (lj) {
+        const double dv = th - pm;
+        pj = dv * dv * pinv;
+      }
+      if (lj2) {
+        const double dv2 = th2 - pm2;
+        pj += dv2 * dv2 * pinv2;
+      }
+      lp_n = -0.5 * (a.logconst + tda_wave_sum(pj));
+#endif
+      post_n = lp_n + ll_n;
+      alive = __builtin_amdgcn_readfirstlane(__builtin_isfinite(post_n) ? 1 : 0);
+      if (!alive) break;
+#ifdef TDA_GRADIENT_WAVE
+      s_grad[lane] = 0.0;  // (its readers of the previous leapfrog step are behind the barriers above)
+      s_grad[lane2] = 0.0;
+#endif
+      __syncthreads();  // s_sens complete
+#ifdef TDA_GRADIENT_WAVE
+      tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
+      __syncthreads();
+      g = lj ? TDA_PRIOR_GRAD(th, pm, pinv, lane) + s_grad[lane] : 0.0;
+      g2 = lj2 ? TDA_PRIOR_GRAD(th2, pm2, pinv2, lane2) + s_grad[lane2] : 0.0;
+#else
+      g = lj ? TDA_PRIOR_GRAD(th, pm, pinv, lane) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+      g2 = lj2 ? TDA_PRIOR_GRAD(th2, pm2, pinv2, lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+#endif
+      const double cc = i < a.n_leapfrog ? eps : he;
+      p += cc * g;
+      p2 += cc * g2;
+    }
+    // a gradient that is not finite leaves a NaN momentum: the next position's log-posterior is NaN and ends the trajectory, or
+    // (at the last step) k1 is NaN, alpha is NaN and `u < NaN` is false
+    const double k1 = 0.5 * tda_wave_sum(w * (p * p) + w2 * (p2 * p2));
+    double alpha = exp((post_n - (lp + ll)) + (k0 - k1));
+    if (!alive || post_n != post_n) alpha = 0.0;
+    const bool acc = a.u[(size_t)s * a.NP + c] < alpha;
+    if (acc) {
+      lp = lp_n;
+      ll = ll_n;
+      cur = th;
+      cur2 = th2;
+      gc = g;
+      gc2 = g2;
+    }
+    nacc += acc ? 1 : 0;
+    const size_t r = (size_t)s * a.N + c;
+    if (lane == 0) {
+      if (a.rec_stats) {
+        a.rec_stats[r * 3 + 0] = lp;
+        a.rec_stats[r * 3 + 1] = ll;
+        a.rec_stats[r * 3 + 2] = lp + ll;
+      }
+      if (a.rec_acc) a.rec_acc[r] = acc ? 1 : 0;
+    }
+    if (a.rec_params && lj) a.rec_params[r * a.d + lane] = cur;
+    if (a.rec_params && lj2) a.rec_params[r * a.d + lane2] = cur2;
+  }
+  if (lane < a.DP) {
+    a.theta[row + lane] = cur;
+    a.grad[row + lane] = gc;
+  }
+  if (lane2 < a.DP) {
+    a.theta[row + lane2] = cur2;
+    a.grad[row + lane2] = gc2;
+  }
+  if (lane == 0) {
+    a.lp[c] = lp;
+    a.ll[c] = ll;
+    if (a.acc_count) a.acc_count[c] += nacc;
+  }
+}
+#else
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserMalaArgs a) {
   extern __shared__ double s_sens[];  // [m] ([2 m] under TDA_LOGLIKE_WAVE: the outputs behind the sensitivities)
   __shared__ double s_th[128];
@@ -725,6 +860,7 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_mala_steps(const UserM
     if (a.acc_count) a.acc_count[c] += nacc;
   }
 }
+#endif  // TDA_USER_HMC
 // gradient of the log-posterior at the current states (init; the padding of a row is written as zero)
 extern "C" __global__ void __launch_bounds__(64) tda_user_mala_grad0(const UserMalaArgs a) {
   extern __shared__ double s_sens[];

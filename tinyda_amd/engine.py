@@ -109,7 +109,8 @@ class Engine:
         self._ck(self.lib.tda_engine_set_level(self.h, level, m, _ptr(A), _ptr(b), _ptr(data), noise_kind, _ptr(noise)))
 
     def set_proposal(self, kind, C_=None, scaling=1.0, adaptive=False, gamma=1.01, period=100, sd=None,
-                     epsilon=1e-6, t0=0, block_moments=False, q_mean=None, state_operator=None, noise_operator=None, spectrum=None):
+                     epsilon=1e-6, t0=0, block_moments=False, q_mean=None, state_operator=None, noise_operator=None, spectrum=None,
+                     n_leapfrog=None, inv_mass=None):
         Cm = None if C_ is None else _f64(C_)
         p = _lib.tda_proposal_params(C.sizeof(_lib.tda_proposal_params), kind, scaling, int(adaptive), period, gamma,
                                      _ptr(Cm), -1.0 if sd is None else sd, epsilon, t0, int(block_moments),
@@ -123,6 +124,15 @@ class Engine:
             V, lam = _f64(spectrum[0]), _f64(spectrum[1])
             assert V.shape == (self.dim, self.dim) and lam.shape == (self.dim,)
             self._ck(self.lib.tda_engine_set_proposal_spectrum(self.h, _ptr(V), _ptr(lam)))
+        if n_leapfrog is not None:  # HMC (kind 7)
+            self.set_hmc(n_leapfrog, inv_mass)
+
+    def set_hmc(self, n_leapfrog, inv_mass=None):
+        """trajectory length and diagonal inverse mass (None: unit mass) of the HMC proposal: after set_proposal(7, ...), before init"""
+        w = None if inv_mass is None else _f64(inv_mass)
+        if w is not None and w.shape != (self.dim,):
+            raise ValueError("inv_mass takes one positive value per parameter")
+        self._ck(self.lib.tda_engine_set_hmc(self.h, int(n_leapfrog), _ptr(w)))
 
     def set_prior_joint(self, kinds, loc, scale):
         """JointPrior of scalar components: kinds[j] 0 = norm(loc, scale), 1 = uniform(loc, scale); or 2 (_lib.PRIOR_SOURCE) for

@@ -13,11 +13,11 @@ import numpy as np
 from . import _lib
 from ._contract import SIG
 from .likelihoods import _is_diagonal
-from .proposals import (DREAM, DREAMZ, MALA, AdaptiveMetropolis, CrankNicolson, GaussianRandomWalk, IndependenceSampler,
+from .proposals import (DREAM, DREAMZ, HMC, MALA, AdaptiveMetropolis, CrankNicolson, GaussianRandomWalk, IndependenceSampler,
                         OperatorWeightedCrankNicolson)
 
 _GRW_PCN_AM = (GaussianRandomWalk, CrankNicolson, AdaptiveMetropolis)
-_DEVICE_PROPOSALS = _GRW_PCN_AM + (DREAMZ, DREAM, IndependenceSampler, OperatorWeightedCrankNicolson, MALA)
+_DEVICE_PROPOSALS = _GRW_PCN_AM + (DREAMZ, DREAM, IndependenceSampler, OperatorWeightedCrankNicolson, MALA, HMC)
 
 MAX_LEVELS = 6  # (0.5; five and six levels: no error model, no dense observation covariance, at most 64 parameters -- MAX_LEVELS_FULL otherwise)
 MAX_LEVELS_FULL = 4
@@ -73,6 +73,12 @@ def _level(low, run):
             or (low["prior_mean"].shape[0] > 64 and _above_64_parameters(low, run)) or _diagonal_error_model_covariance(low, run) or None)
 
 
+# the proposals on the gradient of the log-posterior, MALA and HMC (a subclass: one kernel family, tda_user_mala_steps /
+# tda_user_hmc_steps, one set of rules).  Every rule below that speaks of them takes the name from here
+def _gradient_name(run):
+    return type(run.proposal).__name__ if isinstance(run.proposal, MALA) else None
+
+
 # the rules that a source-defined prior and a DeviceLogLike share: both exist inside the program compiled with a DeviceModel only,
 # so the routes on which the engine's own kernels evaluate the prior or a level's likelihood are closed to them.  `who` is the label
 def _level_cap(who, run):
@@ -107,7 +113,7 @@ def _missing_loglike_gradient(mala, low):
 def _prior_source(low, run):
     who = low["prior_source"]["label"]
     return (_prior_source_models(who, low) or _level_cap(who, run) or _under_dreamz(who, run) or _prior_source_gaussian_proposals(who, run)
-            or (isinstance(run.proposal, MALA) and _prior_source_mala(who, low, run)) or _under_independence(who, run) or _with_error_model(who, run) or _with_randomize(who, run))
+            or (_gradient_name(run) and _prior_source_mala(who, low, run)) or _under_independence(who, run) or _with_error_model(who, run) or _with_randomize(who, run))
 
 
 def _prior_source_models(who, low):
@@ -120,21 +126,22 @@ def _prior_source_gaussian_proposals(who, run):
         return "%s is not lowered under %s (it needs a Gaussian prior)" % (who, type(run.proposal).__name__)
 
 
-# tda_user_mala_steps takes the prior's gradient from the source: a DevicePrior that defines tda_logprior_term_grad
+# tda_user_mala_steps (HMC: tda_user_hmc_steps) takes the prior's gradient from the source: a DevicePrior that defines tda_logprior_term_grad
 # (DevicePrior.from_distributions for scipy families), single level, over a model with its own gradient
 def _prior_source_mala(who, low, run):
+    mala = _gradient_name(run)
     if not low["prior_source"]["has_gradient"]:
         if low["prior_source"].get("coupled"):
-            return "%s is not lowered under MALA: a prior that couples parameters needs %s in its source" % (who, SIG["tda_logprior_grad"])
-        return ("%s is not lowered under MALA: it needs a DevicePrior whose source defines %s (DevicePrior.from_distributions for scipy families)"
-                % (who, SIG["tda_logprior_term_grad"]))
+            return "%s is not lowered under %s: a prior that couples parameters needs %s in its source" % (who, mala, SIG["tda_logprior_grad"])
+        return ("%s is not lowered under %s: it needs a DevicePrior whose source defines %s (DevicePrior.from_distributions for scipy families)"
+                % (who, mala, SIG["tda_logprior_term_grad"]))
     if run.n_levels != 1:
-        return "%s under MALA: single level only" % who
+        return "%s under %s: single level only" % (who, mala)
     if not low["has_gradient"]:
-        return "%s under MALA needs %s (or tda_gradient_wave) in the model source" % (who, SIG["tda_gradient"])
+        return "%s under %s needs %s (or tda_gradient_wave) in the model source" % (who, mala, SIG["tda_gradient"])
     if np.asarray(low["data"]).shape[0] > 2048:
-        return "%s under MALA over a source-defined model: at most 2048 outputs" % who
-    return _missing_loglike_gradient("%s under MALA" % who, low)
+        return "%s under %s over a source-defined model: at most 2048 outputs" % (who, mala)
+    return _missing_loglike_gradient("%s under %s" % (who, mala), low)
 
 
 # a DeviceLogLike: the shared rules, and MALA last
@@ -143,7 +150,7 @@ def _loglike_source(low, run):
     if "loglike_source" not in low:
         return "DeviceLogLike is compiled into the program of its level's model, which must be a DeviceModel"
     return (_level_cap(who, run) or _under_dreamz(who, run) or _loglike_source_owcn(run) or _under_independence(who, run)
-            or _with_error_model(who, run) or _with_randomize(who, run) or (isinstance(run.proposal, MALA) and _loglike_source_mala(low, run)))
+            or _with_error_model(who, run) or _with_randomize(who, run) or (_gradient_name(run) and _loglike_source_mala(low, run)))
 
 
 def _loglike_source_owcn(run):
@@ -152,8 +159,8 @@ def _loglike_source_owcn(run):
 
 def _loglike_source_mala(low, run):
     if run.n_levels != 1 or ("prior_joint" in low and "prior_source" not in low) or not _is_diagonal(low["prior_cov"]):
-        return "MALA with a DeviceLogLike: single level, multivariate normal prior with diagonal covariance or a DevicePrior with its gradient"
-    return _missing_loglike_gradient("MALA", low)
+        return "%s with a DeviceLogLike: single level, multivariate normal prior with diagonal covariance or a DevicePrior with its gradient" % _gradient_name(run)
+    return _missing_loglike_gradient(_gradient_name(run), low)
 
 
 # 65 .. 128 parameters (0.5, tda_kernels_wide.h): single-level chains, Delayed Acceptance and MLDA (up to four levels), linear,
@@ -163,7 +170,7 @@ def _above_64_parameters(low, run):
     n, prop = run.n_levels, type(run.proposal)
     external = "batched" in low or "source" in low
     diagonal_error_model = n >= 2 and run.error_model is not None and run.diagonal_error_model
-    mala_on_source_gradient = prop is MALA and n == 1 and low.get("has_gradient")  # (a source-defined model's tda_gradient)
+    mala_on_source_gradient = prop in (MALA, HMC) and n == 1 and low.get("has_gradient")  # (a source-defined model's tda_gradient)
     other_proposal = prop not in _GRW_PCN_AM and not mala_on_source_gradient
     other_model = (low.get("A") is None and not external) or "rosenbrock" in low  # (linear, source-defined and batched host models)
     dense_prior_of_external = external and not _is_diagonal(low["prior_cov"])  # (external models: diagonal prior covariance, as at any width)
@@ -210,7 +217,7 @@ def _dense_noise(low, run):
 # ---- the hierarchy as a whole --------------------------------------------------------------------------------------------------
 def _hierarchy(lows, run):
     return (_diagonal_error_model_noise(lows, run) or _dense_error_model(lows, run) or _shared_archive(run) or _rosenbrock(lows, run)
-            or _joint_prior(lows, run) or _external_models(lows, run) or (isinstance(run.proposal, MALA) and _mala(lows, run))
+            or _joint_prior(lows, run) or _external_models(lows, run) or (_gradient_name(run) and _mala(lows, run))
             or (isinstance(run.proposal, OperatorWeightedCrankNicolson) and _owcn(lows, run)) or _independence(lows, run) or _one_prior(lows))
 
 
@@ -273,12 +280,14 @@ def _external_models(lows, run):
 # model's own tda_gradient (single level, iso / diag noise, diagonal Gaussian prior or a DevicePrior with its gradient:
 # tda_user_mala_steps)
 def _mala(lows, run):
-    low = lows[0]
+    low, mala = lows[0], _gradient_name(run)
     if run.n_levels == 1 and "source" in low and ("prior_joint" not in low or "prior_source" in low):  # (a source-defined prior: checked by _prior_source)
         if not low["has_gradient"]:
-            return "MALA over a source-defined model needs %s in the model source" % SIG["tda_gradient"]
+            return "%s over a source-defined model needs %s in the model source" % (mala, SIG["tda_gradient"])
         if low["noise_kind"] not in _ISO_DIAG + (_lib.NOISE_SOURCE,) or np.asarray(low["data"]).shape[0] > 2048:
-            return "MALA over a source-defined model: isotropic or diagonal noise, at most 2048 outputs"
+            return "%s over a source-defined model: isotropic or diagonal noise, at most 2048 outputs" % mala
+    elif isinstance(run.proposal, HMC):  # (the engine's linear-model MALA, k_mh_steps with its closed-form gradient, has no leapfrog loop)
+        return "HMC: single level, a DeviceModel with tda_gradient, Gaussian prior with diagonal covariance or a DevicePrior with its gradient"
     elif run.n_levels != 1 or "source" in low or "batched" in low or "rosenbrock" in low or "prior_joint" in low:
         return "MALA: single level, linear model, Gaussian prior"
 

@@ -269,6 +269,68 @@ class MALA(GaussianRandomWalk):
                     gamma=float(self.gamma), period=int(self.period))
 
 
+class HMC(MALA):
+    """Hamiltonian Monte Carlo (an extension: the reference has none): per proposal a momentum p = z / sqrt(w) from d unit normals
+    z, `n_leapfrog` leapfrog steps of size `scaling` under the diagonal inverse mass w = `inv_mass` (None: 1) on the log-posterior
+    and the gradient that MALA uses (exact or finite differences, chosen as MALA chooses), and one accept test on the energy
+    difference, alpha = exp(post' - post + K0 - K1) with K = 1/2 sum_j w_j p_j^2.  A position whose log-posterior is NaN or infinite
+    ends the trajectory and rejects.  With one step and unit mass this is MALA.  `adaptive` adapts the step size towards 0.65
+    acceptance.  On the device path (a single-level DeviceModel with `tda_gradient`, wherever MALA lowers) the whole trajectory
+    runs in one kernel, tda_user_hmc_steps; over any other model the host protocol below runs."""
+
+    alpha_star = 0.65
+
+    def __init__(self, scaling=0.1, n_leapfrog=8, inv_mass=None, adaptive=False, gamma=1.01, period=100):
+        if int(n_leapfrog) != n_leapfrog or not 1 <= n_leapfrog <= 1024:
+            raise ValueError("n_leapfrog must be an integer in 1 .. 1024, not %r" % (n_leapfrog,))
+        if inv_mass is not None:
+            inv_mass = np.atleast_1d(np.asarray(inv_mass, dtype=np.float64)).copy()
+            if inv_mass.ndim != 1 or not np.all(np.isfinite(inv_mass) & (inv_mass > 0)):
+                raise ValueError("inv_mass takes one finite, positive value per parameter")
+        self.n_leapfrog, self.inv_mass = int(n_leapfrog), inv_mass
+        self._init_scaling(scaling, adaptive, gamma, period)
+
+    def setup_proposal(self, **kwargs):
+        super().setup_proposal(**kwargs)
+        if self.inv_mass is not None and self.inv_mass.shape != (self.d,):
+            raise ValueError("inv_mass has %d entries for %d parameters" % (self.inv_mass.shape[0], self.d))
+
+    def make_proposal(self, link):
+        if not hasattr(link, "gradient"):
+            link.gradient = self.compute_gradient(link)
+        eps, w = self.scaling, np.ones(self.d) if self.inv_mass is None else self.inv_mass
+        p = np.random.standard_normal(self.d) / np.sqrt(w)
+        k0 = 0.5 * np.sum(w * (p * p))
+        p = p + (0.5 * eps) * link.gradient
+        theta = np.asarray(link.parameters, dtype=np.float64)
+        self._end = None  # (the end point, its gradient, K0 - K1): None when the trajectory ended early
+        for i in range(1, self.n_leapfrog + 1):
+            theta = theta + eps * (w * p)
+            at = self.posterior.create_link(theta)
+            if not np.isfinite(at.posterior):
+                return theta
+            grad = self.compute_gradient(at)
+            p = p + (eps if i < self.n_leapfrog else 0.5 * eps) * grad
+        self._end = (theta, grad, k0 - 0.5 * np.sum(w * (p * p)))
+        return theta
+
+    def get_acceptance(self, proposal_link, previous_link):
+        end = getattr(self, "_end", None)
+        if end is None or end[0] is not proposal_link.parameters and not np.array_equal(end[0], proposal_link.parameters):
+            return 0
+        if np.isnan(proposal_link.posterior):
+            return 0
+        proposal_link.gradient = end[1]
+        return np.exp((proposal_link.posterior - previous_link.posterior) + end[2])
+
+    def get_q(self, x_link, y_link):  # (the momentum is not part of a link: the energy difference is inside get_acceptance)
+        return 0.0
+
+    def _lowering(self):
+        return dict(kind=_lib.PROP_HMC, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
+                    period=int(self.period), n_leapfrog=self.n_leapfrog, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+
+
 class AdaptiveMetropolis(GaussianRandomWalk):
     """Haario et al. (2001): proposal covariance <- running sample covariance every `period` adapt calls
     once t >= t0 (proposal.py:372-512).
