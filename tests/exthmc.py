@@ -107,19 +107,22 @@ def run_hmc(level, prop, theta0, z, u, perturb=False):
     return dict(theta=out_theta, logprior=out_lp, loglike=out_ll, logpost=out_lp + out_ll, accepted=out_acc, scaling=eps, ended=ended, dH=dH)
 
 
-def assert_admissible(level, prop, theta0, z, u, ref=None):
+def assert_admissible(level, prop, theta0, z, u, ref=None, state_share=None):
     """A leapfrog map that is not stable amplifies last-bit differences, and then no tolerance holds: a case is compared only if
     the twin with every gradient moved by one ulp gives the same masks and log-posteriors within 1e-11, and the twin's
-    acceptance rate lies in [0.1, 0.9].  -> the unperturbed trace"""
+    acceptance rate lies in [0.1, 0.9].  state_share: the one ulp moves no state by more than this share of the bar the states are
+    compared at (1e-12 + 1e-9 |state|).  -> the unperturbed trace"""
     ref = run_hmc(level, prop, theta0, z, u) if ref is None else ref
     moved = run_hmc(level, prop, theta0, z, u, perturb=True)
     rate = ref["accepted"][:, 1:].mean()
     err = np.max(np.abs(moved["logpost"] / ref["logpost"] - 1.0))
-    print("twin: acceptance %.3f, trajectories ended early %d of %d, one ulp on every gradient moves the log-posterior by %.1e"
-          % (rate, np.count_nonzero(ref["ended"]), ref["ended"].size, err))
+    share = np.max(np.abs(moved["theta"] - ref["theta"]) / (1e-12 + 1e-9 * np.abs(ref["theta"])))
+    print("twin: acceptance %.3f, trajectories ended early %d of %d, one ulp on every gradient moves the log-posterior by %.1e and the states "
+          "by %.1e of their bar" % (rate, np.count_nonzero(ref["ended"]), ref["ended"].size, err, share))
     assert np.array_equal(moved["accepted"], ref["accepted"])
     assert err <= 1e-11, err
     assert 0.1 <= rate <= 0.9, rate
+    assert state_share is None or share <= state_share, share
     return ref
 
 

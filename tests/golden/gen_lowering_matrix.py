@@ -50,7 +50,7 @@ LIKE_OUTPUTS = {"iso": 3, "diag": 3, "dense": 3, "adaptive": 3, "adaptive_dense"
 PRIORS = ("mvn", "mvn_dense", "mvn_shifted", "joint", "joint_families", "dp_term", "dp_term_grad", "dp_wave", "dp_wave_nograd",
           "dp_families", "dp_term_other", "scalar")
 PROPOSALS = ("grw", "grw_adaptive", "pcn", "am", "am_block", "dreamz", "dreamz_lhs", "dreamz_other", "dream", "indep", "indep_other",
-             "owcn", "owcn_adaptive", "owcn_adaptive_other", "mala", "subclass")
+             "owcn", "owcn_adaptive", "owcn_adaptive_other", "mala", "hmc", "subclass")
 ERROR_MODELS = ("-", "si", "sd", "diag")  # none, state-independent, state-dependent, state-independent with the diagonal covariance
 
 
@@ -161,6 +161,8 @@ def proposal(name, d):
         return tda.OperatorWeightedCrankNicolson(0.5 * np.eye(d) + np.triu(0.1 * np.ones((d, d)), 1), scaling=0.5, adaptive=True)
     if name == "mala":
         return tda.MALA(0.05)
+    if name == "hmc":
+        return tda.HMC(0.05, n_leapfrog=3)
     return _Subclass(np.eye(d))
 
 
@@ -188,7 +190,7 @@ SINGLE_PRIORS = tuple(p for p in PRIORS if p not in ("mvn_shifted", "dp_term_oth
 HIER_MODELS = ("lin4", "lin100", "wrapped", "batched", "dev", "dev100", "dev_wave_gradwave")
 HIER_LIKES = ("iso", "diag", "dense", "ll_term", "ll_wave_nograd")
 HIER_PRIORS = ("mvn", "mvn_dense", "joint", "joint_families", "dp_term_grad", "dp_wave", "dp_families")
-HIER_PROPOSALS = ("grw", "grw_adaptive", "pcn", "am", "am_block", "dreamz", "dream", "indep", "owcn", "mala", "subclass")
+HIER_PROPOSALS = ("grw", "grw_adaptive", "pcn", "am", "am_block", "dreamz", "dream", "indep", "owcn", "mala", "hmc", "subclass")
 HIER_THINNING = {2: 24, 3: 48, 4: 96, 5: 48, 6: 96, 7: 192}  # one case in ... of the product
 # levels of the mixed two-level hierarchies (the mixtures the other tests build: adaptive coarse under isotropic fine, batched
 # plus linear, Gaussian coarse plus DeviceLogLike fine, levels with different priors)
@@ -196,7 +198,7 @@ MIXED_LEVELS = (("lin4", "iso", "mvn"), ("lin4", "adaptive", "mvn"), ("lin4", "d
                 ("batched", "iso", "mvn"), ("wrapped", "adaptive", "mvn"), ("dev", "iso", "mvn"), ("dev", "ll_term", "mvn"), ("dev", "ll_wave", "mvn"),
                 ("dev", "iso", "dp_term"), ("dev", "ll_term", "dp_term"), ("dev", "diag", "dp_term_other"), ("dev_wave", "iso", "dp_wave"),
                 ("dev", "adaptive", "joint"), ("lin4", "iso", "joint"), ("rosen", "iso", "mvn"))
-MIXED_PROPOSALS = ("grw", "pcn", "am", "dreamz", "dream", "mala")
+MIXED_PROPOSALS = ("grw", "pcn", "am", "dreamz", "dream", "mala", "hmc")
 # single cases: the rules that only a particular size, or a particular pair of levels, reaches
 _L, _A = ("lin4", "iso", "mvn"), ("lin4", "adaptive", "mvn")
 EXTRA = (
@@ -306,6 +308,7 @@ def names_digest(names):
 
 # ---- the refusal sites of the pass, in the order of the code; each is recognised by its text ------------------------------------
 _WHO = r"(DevicePrior|JointPrior of scipy families \(source-defined prior\))"
+_GRAD = r"(MALA|HMC)"  # the proposals on the gradient of the log-posterior share their rules, each worded with its own name
 SITES = (
     ("levels or proposal class", r"more than 6 levels \(or none\), or a proposal class"),
     ("five / six levels: error model, DREAM(Z)", r"more than 4 levels are lowered without error model"),
@@ -315,13 +318,13 @@ SITES = (
     ("prior: level cap", _WHO + r": hierarchies of at most 4 levels"),
     ("prior: DREAM(Z)", _WHO + r" is not lowered under DREAM\(Z\)"),
     ("prior: pCN / OWCN", _WHO + r" is not lowered under \w+ \(it needs a Gaussian prior\)"),
-    ("prior: MALA, coupled without gradient", _WHO + r" is not lowered under MALA: a prior that couples parameters needs"),
-    ("prior: MALA, term without gradient", _WHO + r" is not lowered under MALA: it needs a DevicePrior whose source defines"),
-    ("prior: MALA, single level", _WHO + r" under MALA: single level only"),
-    ("prior: MALA, model gradient", _WHO + r" under MALA needs __device__ double tda_gradient"),
-    ("prior: MALA, 2048 outputs", _WHO + r" under MALA over a source-defined model: at most 2048 outputs"),
-    ("prior: MALA, coupled likelihood gradient", _WHO + r" under MALA with a DeviceLogLike that couples outputs needs"),
-    ("prior: MALA, likelihood term gradient", _WHO + r" under MALA with a DeviceLogLike needs"),
+    ("prior: MALA, coupled without gradient", _WHO + r" is not lowered under " + _GRAD + r": a prior that couples parameters needs"),
+    ("prior: MALA, term without gradient", _WHO + r" is not lowered under " + _GRAD + r": it needs a DevicePrior whose source defines"),
+    ("prior: MALA, single level", _WHO + r" under " + _GRAD + r": single level only"),
+    ("prior: MALA, model gradient", _WHO + r" under " + _GRAD + r" needs __device__ double tda_gradient"),
+    ("prior: MALA, 2048 outputs", _WHO + r" under " + _GRAD + r" over a source-defined model: at most 2048 outputs"),
+    ("prior: MALA, coupled likelihood gradient", _WHO + r" under " + _GRAD + r" with a DeviceLogLike that couples outputs needs"),
+    ("prior: MALA, likelihood term gradient", _WHO + r" under " + _GRAD + r" with a DeviceLogLike needs"),
     ("prior: IndependenceSampler", _WHO + r" is not lowered under IndependenceSampler"),
     ("prior: error model", _WHO + r" is not lowered together with an adaptive error model"),
     ("prior: randomize", _WHO + r" is not lowered with randomize_subchain_length"),
@@ -332,9 +335,9 @@ SITES = (
     ("likelihood: IndependenceSampler", r"DeviceLogLike is not lowered under IndependenceSampler"),
     ("likelihood: error model", r"DeviceLogLike is not lowered together with an adaptive error model"),
     ("likelihood: randomize", r"DeviceLogLike is not lowered with randomize_subchain_length"),
-    ("likelihood: MALA, level / prior", r"MALA with a DeviceLogLike: single level, multivariate normal prior"),
-    ("likelihood: MALA, coupled gradient", r"MALA with a DeviceLogLike that couples outputs needs"),
-    ("likelihood: MALA, term gradient", r"MALA with a DeviceLogLike needs"),
+    ("likelihood: MALA, level / prior", _GRAD + r" with a DeviceLogLike: single level, multivariate normal prior"),
+    ("likelihood: MALA, coupled gradient", _GRAD + r" with a DeviceLogLike that couples outputs needs"),
+    ("likelihood: MALA, term gradient", _GRAD + r" with a DeviceLogLike needs"),
     ("more than 64 parameters", r"more than 64 parameters are lowered for"),
     ("diagonal error model: adaptive covariances", r"error_model_covariance='diagonal' needs diagonal covariances"),
     ("adaptive likelihood: hierarchy, outputs", r"AdaptiveGaussianLogLike on the device: coarse levels"),
@@ -352,8 +355,9 @@ SITES = (
     ("external models: level cap", r"hierarchies of callback / source-defined models: at most 4 levels"),
     ("external models: proposals of a hierarchy", r"hierarchies of callback / source-defined models run under"),
     ("external models: noise / prior covariance", r"callback / source-defined models need isotropic / diagonal noise"),
-    ("MALA: model gradient", r"MALA over a source-defined model needs"),
-    ("MALA: source-defined model, noise / outputs", r"MALA over a source-defined model: isotropic or diagonal noise"),
+    ("MALA: model gradient", _GRAD + r" over a source-defined model needs"),
+    ("MALA: source-defined model, noise / outputs", _GRAD + r" over a source-defined model: isotropic or diagonal noise"),
+    ("HMC: otherwise", r"HMC: single level, a DeviceModel with tda_gradient"),
     ("MALA: otherwise", r"MALA: single level, linear model, Gaussian prior"),
     ("OWCN: level / operators", r"OperatorWeightedCrankNicolson: single level, operators"),
     ("OWCN: adaptive", r"adaptive OperatorWeightedCrankNicolson \(per-chain operators\)"),
