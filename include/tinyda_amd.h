@@ -92,8 +92,10 @@ typedef enum tda_proposal_kind {
   TDA_PROP_INDEPENDENCE = 4, /* IndependenceSampler with a Gaussian q (proposal.py:65-129) */
   TDA_PROP_OWCN = 5,         /* OperatorWeightedCrankNicolson with fixed operators (proposal.py:515-605) */
   TDA_PROP_MALA = 6,         /* MALA with the exact gradient of a linear-Gaussian posterior (proposal.py:861-1005): scaling = sigma */
-  TDA_PROP_HMC = 7           /* Hamiltonian Monte Carlo over a single-level source-defined model with its gradient (an extension: the reference has
+  TDA_PROP_HMC = 7,          /* Hamiltonian Monte Carlo over a single-level source-defined model with its gradient (an extension: the reference has
                               * none): scaling = the leapfrog step size, adaptive towards 0.65 acceptance; trajectory length and mass: tinyda_amd_hmc.h */
+  TDA_PROP_NUTS = 8          /* the no-U-turn sampler over what HMC takes (an extension as well): scaling = the leapfrog step size, adaptive on the
+                              * trees' acceptance statistic; tree depth, target and mass: tinyda_amd_nuts.h */
 } tda_proposal_kind;
 
 typedef struct tda_config {

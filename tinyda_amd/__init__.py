@@ -23,7 +23,7 @@ from .records import Link  # noqa: F401
 from .models import BatchedModel, DeviceModel, LinearModel, Rosenbrock  # noqa: F401
 from .target import Posterior  # noqa: F401
 from .proposals import (  # noqa: F401
-    DREAM, DREAMZ, HMC, MALA, AdaptiveMetropolis, CrankNicolson, GaussianRandomWalk, IndependenceSampler,
+    DREAM, DREAMZ, HMC, MALA, NUTS, AdaptiveMetropolis, CrankNicolson, GaussianRandomWalk, IndependenceSampler,
     OperatorWeightedCrankNicolson, Proposal)
 from .records import DeviceChain  # noqa: F401
 from .api import HostFallbackWarning, release_cached_memory, sample  # noqa: F401

@@ -17,6 +17,7 @@ PRIOR_NORMAL, PRIOR_UNIFORM, PRIOR_SOURCE = 0, 1, 2  # kinds of set_prior_joint;
 AEM_NONE, AEM_STATE_INDEPENDENT, AEM_STATE_DEPENDENT, AEM_STATE_INDEPENDENT_DIAGONAL = 0, 1, 2, 3
 PROP_GRW, PROP_PCN, PROP_AM, PROP_DREAMZ, PROP_INDEPENDENCE, PROP_OWCN, PROP_MALA = 0, 1, 2, 3, 4, 5, 6
 PROP_HMC = 7  # Hamiltonian Monte Carlo over a source-defined model (proposals.HMC; include/tinyda_amd_hmc.h)
+PROP_NUTS = 8  # the no-U-turn sampler over what HMC takes (proposals.NUTS; include/tinyda_amd_nuts.h)
 
 
 class EngineError(RuntimeError):
@@ -207,6 +208,12 @@ HMC_SYMBOLS = {
     "tda_engine_set_hmc": (C.c_int, [_P, C.c_int32, _P]),
 }
 
+# every symbol include/tinyda_amd_nuts.h declares: bound by load() only (the CPU build of the ABI has no NUTS)
+NUTS_SYMBOLS = {
+    "tda_engine_set_nuts": (C.c_int, [_P, C.c_int32, C.c_double, _P]),
+    "tda_engine_get_nuts_totals": (C.c_int, [_P, _P]),
+}
+
 _lib = None
 
 
@@ -248,7 +255,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # missing ROCm runtime etc.
         raise EngineError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()) + list(NUTS_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

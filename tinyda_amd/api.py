@@ -387,7 +387,38 @@ class LazyProposalState(Mapping):
         return _materialised_proposal_state(copy.deepcopy(dict(self._load()), memo), self._shape, self._want_am)
 
 
+class NutsProposalState(LazyProposalState):
+    """result['proposal_state'] of a NUTS run: the lazy state above and, per chain, the totals of the run's trees -- `n_leapfrog`
+    (leapfrog steps, discarded and divergent leaves included), `n_divergent` (trees ended by a divergent leaf), `n_max_depth`
+    (trees that completed max_depth doublings) and `mean_tree_depth` (merged doublings per step).  The totals stay in device
+    memory ([n_chains, 4] int64, copied out of the engine before it closes) until the state is first indexed."""
+
+    _KEYS = ("n_leapfrog", "n_divergent", "n_max_depth", "mean_tree_depth")
+
+    def __init__(self, snapshot, n_chains, dim, totals, steps):
+        super().__init__(snapshot, n_chains, dim, False)
+        self._totals, self._steps = totals, steps
+
+    def _load(self):
+        if self._totals is not None:
+            tot = self._totals.cpu().numpy()
+            data = dict(super()._load(), n_leapfrog=tot[:, 0].copy(), n_divergent=tot[:, 1].copy(), n_max_depth=tot[:, 2].copy(),
+                        mean_tree_depth=tot[:, 3] / float(max(self._steps, 1)))
+            self._data, self._totals = data, None
+        return self._data
+
+    def __iter__(self):
+        return iter(tuple(super().__iter__()) + self._KEYS)
+
+    def __len__(self):
+        return super().__len__() + len(self._KEYS)
+
+
 def _materialised_proposal_state(data, shape, want_am):
+    if "n_leapfrog" in data:
+        st = NutsProposalState(None, shape[0], shape[1], None, 0)
+        st._data = data
+        return st
     st = LazyProposalState(None, shape[0], shape[1], want_am)
     st._data = data
     return st
@@ -511,6 +542,10 @@ def _sample_device(plan, posterior, iterations, n_chains, initial_parameters, se
             eng.run(T, params[1:], stat[1:], acc[1:])
         if prop["kind"] == _lib.PROP_DREAMZ:
             state = dict(eng.dreamz_state(), scaling=eng.proposal_state_scaling())
+        elif prop["kind"] == _lib.PROP_NUTS:
+            with torch.cuda.device(tdev):
+                totals = eng.nuts_totals(torch.empty((N, 4), dtype=torch.int64, device=tdev))
+            state = NutsProposalState(eng.detach_proposal_state(), N, d, totals, T)
         else:
             state = LazyProposalState(eng.detach_proposal_state(), N, d, prop["kind"] == _lib.PROP_AM)
     finally:

@@ -362,6 +362,12 @@ struct tda_engine {
   int hmc_n_leapfrog = 8;
   std::vector<double> hmc_inv_mass_h;  // [d]; empty: unit mass
   DevBuf<double> hmc_inv_mass;         // [DP], ones in the padding (uploaded by tda_engine_init)
+  // NUTS (TDA_PROP_NUTS, tda_engine_set_nuts): the mass is HMC's pair above; the per-chain sums are chain state of a NUTS engine
+  // alone (allocated by its tda_engine_init, so no other engine's checkpoint blob holds them)
+  int nuts_max_depth = 8;
+  double nuts_target = 0.8;
+  DevBuf<double> nuts_accsum;      // [NP]: the running period's sum of acceptance statistics
+  DevBuf<long long> nuts_totals;   // [NP][TDA_NUTS_TOTALS]
   DevBuf<double> q_mean_d, lq, qzblk, qzblk2[2];
   double am_sd = 1.0;
   bool L_shared = true;
@@ -1025,7 +1031,24 @@ int fill_user_hmc_args(tda_engine* e, const Level& lv, UserHmcArgs& ha) {
 
 // the proposals that run on the gradient of the log-posterior: MALA, and HMC (source-defined models only: tda_engine_init
 // refuses it over anything else, so that every branch below that HMC shares with MALA is the source-defined one)
-inline bool gradient_proposal(int kind) { return kind == TDA_PROP_MALA || kind == TDA_PROP_HMC; }
+inline bool gradient_proposal(int kind) { return kind == TDA_PROP_MALA || kind == TDA_PROP_HMC || kind == TDA_PROP_NUTS; }
+// HMC and NUTS: the leapfrog proposals, lowered over a source-defined model only and refused in HMC's words under their own name
+inline bool leapfrog_proposal(int kind) { return kind == TDA_PROP_HMC || kind == TDA_PROP_NUTS; }
+inline const char* gradient_proposal_name(int kind) { return kind == TDA_PROP_NUTS ? "NUTS" : kind == TDA_PROP_HMC ? "HMC" : "MALA"; }
+
+// NUTS over a source-defined model: MALA's arguments, the tree's configuration and the per-chain sums (the block's Philox
+// position, the records and the adaptation of a period boundary are the launch's: tda_host_single.inc)
+int fill_user_nuts_args(tda_engine* e, const Level& lv, UserNutsArgs& na) {
+  if (int rc = fill_user_mala_args(e, lv, na)) return rc;
+  na.max_depth = e->nuts_max_depth;
+  na.ck_off = (int)(user_mala_lds(lv.uprog_mala.spec, na.m) / sizeof(double));
+  na.inv_mass = e->hmc_inv_mass.p;
+  na.seed = e->cfg.seed;
+  na.chain_offset = e->cfg.chain_offset;
+  na.accsum = e->nuts_accsum.p;
+  na.totals = e->nuts_totals.p;
+  return TDA_OK;
+}
 
 constexpr int MODEL_CALLBACK = 3;
 
@@ -1139,6 +1162,7 @@ UserProgramSpec user_program_spec(const tda_engine* e, const Level& lv, bool mal
   s.forward_wave = lv.forms.forward_wave;
   s.gradient_wave = mala && lv.forms.gradient_wave;
   s.hmc = mala && e->pp.kind == TDA_PROP_HMC;
+  s.nuts = mala && e->pp.kind == TDA_PROP_NUTS;
   return s;
 }
 
@@ -1399,3 +1423,4 @@ int64_t tda_release_cached_memory(void) { return (int64_t)g_pool.trim(); }
 #include "tda_host_replay.inc"
 #include "tda_host_optimize.inc"
 #include "tda_host_hmc.inc"
+#include "tda_host_nuts.inc"

@@ -20,7 +20,7 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     if (gradient_proposal(e->pp.kind)) {  // tda_user_mala_steps / tda_user_hmc_steps take the prior's own gradient from the level's source (single level: set_proposal)
       const UserForms& f0 = e->levels[0].forms;
       if (f0.prior_wave ? !f0.prior_grad : !f0.prior_term_grad)
-        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under %s needs %s in the level's source", e->pp.kind == TDA_PROP_HMC ? "HMC" : "MALA",
+        return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under %s needs %s in the level's source", gradient_proposal_name(e->pp.kind),
                     f0.prior_wave ? TDA_SIG_LOGPRIOR_GRAD : TDA_SIG_LOGPRIOR_TERM_GRAD);
     }
     if (e->pp.kind == TDA_PROP_INDEPENDENCE) return fail(TDA_ERR_UNSUPPORTED, "a source-defined prior under the Independence proposal is not lowered");
@@ -64,10 +64,9 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   }
   if (e->prop_set && !e->is_dreamz && gradient_proposal(e->pp.kind)) {
     const Level& l0 = e->levels[0];
-    const bool hmc = e->pp.kind == TDA_PROP_HMC;
-    const char* const gname = hmc ? "HMC" : "MALA";
-    if (hmc && l0.model != MODEL_USER)  // (k_mh_steps has MALA's closed-form gradient of the linear model and no leapfrog loop)
-      return fail(TDA_ERR_UNSUPPORTED, "HMC is lowered for source-defined forward models with tda_gradient only (the built-in linear model has MALA)");
+    const char* const gname = gradient_proposal_name(e->pp.kind);
+    if (leapfrog_proposal(e->pp.kind) && l0.model != MODEL_USER)  // (k_mh_steps has MALA's closed-form gradient of the linear model and no leapfrog loop)
+      return fail(TDA_ERR_UNSUPPORTED, "%s is lowered for source-defined forward models with tda_gradient only (the built-in linear model has MALA)", gname);
     if (l0.model != MODEL_LINEAR && l0.model != MODEL_USER)
       return fail(TDA_ERR_UNSUPPORTED, "MALA is lowered for linear and source-defined forward models only (exact gradient)");
     if (e->prior_bounded) return fail(TDA_ERR_UNSUPPORTED, "%s needs a Gaussian prior", gname);
@@ -274,6 +273,16 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
   const bool user_mala = mala && e->levels[0].model == MODEL_USER;  // (HMC: always, the refusals above)
   // the second program (the MALA program, or under HMC the HMC program): GRW / pCN / AM engines never build it
   if (user_mala && (rc = ensure_user_program(e, e->levels[0], true))) return rc;
+  if (user_mala && e->pp.kind == TDA_PROP_NUTS) {  // the U-turn checkpoints are dynamic LDS behind the MALA program's: 64 KiB per chain with them
+    const Level& l0 = e->levels[0];
+    const size_t dyn = user_mala_lds(l0.uprog_mala.spec, l0.m), ck = user_nuts_checkpoint_lds(e->nuts_max_depth, DP);
+    int stat = 0;
+    HIP_TRY(hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, l0.uprog_mala.steps));
+    if ((size_t)stat + dyn + ck > USER_LDS_MAX)
+      return fail(TDA_ERR_UNSUPPORTED, "NUTS over a source-defined model holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient and "
+                                       "TDA_WORKSPACE) + %zu bytes for its %d outputs + %zu bytes for the checkpoints of max_depth = %d over %d padded parameters",
+                  stat, dyn, l0.m, ck, e->nuts_max_depth, DP);
+  }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;
   const double* Cuse = (e->pp.kind == TDA_PROP_PCN || owcn) ? e->prior_cov_h.data() : e->prop_C_h.data();  // proposal.py:336-341
@@ -288,7 +297,15 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     // source-defined model: the gradient comes from the model's own tda_gradient at every step (tda_user_mala_steps)
     if ((rc = e->mala_grad.alloc((size_t)NP * DP))) return rc;
     HIP_TRY(hipMemsetAsync(e->mala_grad.p, 0, (size_t)NP * DP * sizeof(double), e->stream));
-    if (e->pp.kind == TDA_PROP_HMC) {  // the diagonal inverse mass, ones in the padding (and everywhere without tda_engine_set_hmc's array)
+    if (e->pp.kind == TDA_PROP_NUTS) {  // the per-chain sums: chain state of a NUTS engine alone
+      if ((rc = e->nuts_accsum.alloc((size_t)NP)) || (rc = e->nuts_totals.alloc((size_t)NP * TDA_NUTS_TOTALS))) return rc;
+      HIP_TRY(hipMemsetAsync(e->nuts_accsum.p, 0, (size_t)NP * sizeof(double), e->stream));
+      HIP_TRY(hipMemsetAsync(e->nuts_totals.p, 0, (size_t)NP * TDA_NUTS_TOTALS * sizeof(long long), e->stream));
+    } else {
+      e->nuts_accsum.release();
+      e->nuts_totals.release();
+    }
+    if (leapfrog_proposal(e->pp.kind)) {  // the diagonal inverse mass, ones in the padding (and everywhere without tda_engine_set_hmc's / set_nuts's array)
       std::vector<double> wm(DP, 1.0);
       for (int j = 0; j < d && !e->hmc_inv_mass_h.empty(); ++j) wm[j] = e->hmc_inv_mass_h[j];
       if ((rc = e->hmc_inv_mass.upload(wm))) return rc;

@@ -233,7 +233,7 @@ int tda_engine_set_proposal(tda_engine* e, const tda_proposal_params* p) {
   if (!e || !p) return fail(TDA_ERR_INVALID, "null argument");
   if (p->struct_size != sizeof(tda_proposal_params)) return fail(TDA_ERR_INVALID, "tda_proposal_params.struct_size mismatch");
   const bool indep = p->kind == TDA_PROP_INDEPENDENCE, owcn = p->kind == TDA_PROP_OWCN, mala = gradient_proposal(p->kind);
-  const char* const gname = p->kind == TDA_PROP_HMC ? "HMC" : "MALA";
+  const char* const gname = gradient_proposal_name(p->kind);
   if ((p->kind < TDA_PROP_GRW || p->kind > TDA_PROP_AM) && !indep && !owcn && !mala) return fail(TDA_ERR_UNSUPPORTED, "proposal kind %d", p->kind);
   if (mala && e->nlev != 1) return fail(TDA_ERR_UNSUPPORTED, "%s is lowered for single-level chains only", gname);
   if (mala && !(p->scaling > 0.0)) return fail(TDA_ERR_INVALID, "%s: scaling must be positive", gname);
@@ -260,6 +260,11 @@ int tda_engine_set_proposal(tda_engine* e, const tda_proposal_params* p) {
   }
   if (p->kind == TDA_PROP_HMC) {  // the defaults of tda_engine_set_hmc, which follows
     e->hmc_n_leapfrog = 8;
+    e->hmc_inv_mass_h.clear();
+  }
+  if (p->kind == TDA_PROP_NUTS) {  // the defaults of tda_engine_set_nuts, which follows
+    e->nuts_max_depth = 8;
+    e->nuts_target = 0.8;
     e->hmc_inv_mass_h.clear();
   }
   if (p->C) e->prop_C_h.assign(p->C, p->C + (size_t)e->d * e->d);

@@ -354,6 +354,24 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
         int xrc = ext_step(e, lv, xa);
         if (xrc) return xrc;
       }
+    } else if (lv.model == MODEL_USER && e->pp.kind == TDA_PROP_NUTS) {  // (the NUTS program stands in the MALA program's place as well)
+      UserNutsArgs na{};
+      int urc = fill_user_nuts_args(e, lv, na);
+      if (urc) return urc;
+      na.S = (int)S;
+      na.inc = sa.inc;
+      na.step0 = e->t;
+      na.rec_params = sa.rec_params;
+      na.rec_stats = sa.rec_stats;
+      na.rec_acc = sa.rec_acc;
+      if (adaptive && (e->t + S) % period == 0) {  // the period ends with this launch: the kernel applies the engine's rule itself, on its acceptance statistic
+        na.scaling_out = e->scaling.p;
+        na.period = period;
+        na.gamma_pow = std::pow(e->pp.gamma, -(double)e->k_adapt);
+        na.alpha_star = e->nuts_target;
+      }
+      ScopedTimer tm(e, 1);
+      if ((urc = launch_user(lv.uprog_mala.steps, na, user_mala_lds(lv.uprog_mala.spec, na.m) + user_nuts_checkpoint_lds(na.max_depth, na.DP), e->stream))) return urc;
     } else if (lv.model == MODEL_USER && e->pp.kind == TDA_PROP_HMC) {  // (the HMC program stands in the MALA program's place: ensure_user_program)
       UserHmcArgs ha{};
       int urc = fill_user_hmc_args(e, lv, ha);
@@ -403,7 +421,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     }
     // ---- adaptation (proposal.py:228-245, :502-512) ----
     const bool boundary = periodic && ((e->t + S) % period == 0);
-    if (is_am || (boundary && adaptive)) {
+    if (is_am || (boundary && adaptive && e->pp.kind != TDA_PROP_NUTS)) {  // (NUTS: tda_user_nuts_steps has adapted already; the count of moves is reset below)
       AdaptArgs aa{};
       aa.N = N;
       aa.NP = NP;

@@ -89,6 +89,8 @@ void enumerate_state(tda_engine* e, std::vector<StateItem>& v) {
   dev(e->am_sigma);
   dev(e->lq);
   dev(e->mala_grad);
+  dev(e->nuts_accsum);  // (a NUTS engine alone holds these two: the running period's acceptance sum and the per-chain totals)
+  dev(e->nuts_totals);
   if (e->nlev > 1) {
     host(e->cnt, sizeof e->cnt);
     host(e->done, sizeof e->done);

@@ -104,6 +104,25 @@ struct UserHmcArgs : UserMalaArgs {
   const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding
 };
 
+// NUTS over a source-defined model (tda_user_nuts_steps; the algorithm: include/tinyda_amd_nuts.h): MALA's chain state, unit
+// normals and records (`u` is not read), the tree's configuration, the Philox position of the launch's first step for the tree
+// draws (stream 8), and the per-chain sums that outlive a launch.  `scaling` is the leapfrog step size.
+#define TDA_NUTS_MAX_DEPTH 10
+#define TDA_NUTS_TOTALS 4  // per chain: leapfrog steps, divergent trees, trees that completed max_depth doublings, sum of tree depths
+struct UserNutsArgs : UserMalaArgs {
+  int max_depth;           // doublings per tree at the most, 1 .. TDA_NUTS_MAX_DEPTH
+  int ck_off;              // where the checkpoints start in the dynamic LDS, in doubles (behind the MALA program's s_sens)
+  const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding
+  unsigned long long seed;
+  long long step0, chain_offset;  // global step of this launch's step 0; global id of chain 0
+  double* accsum;          // [NP]: the running period's sum of per-step acceptance statistics
+  long long* totals;       // [NP][TDA_NUTS_TOTALS]
+  double* scaling_out;     // the launch ends a period of an adaptive proposal: scaling <- exp(log scaling + gamma_pow (accsum / period -
+                           // alpha_star)) and accsum <- 0 (null: neither)
+  int period;
+  double gamma_pow, alpha_star;
+};
+
 // The replay of recorded parameters through the model (tda_user_replay): outputs and quantities of interest of the rows
 // [0, R) of N chains, one wave per chain and segment of `seg` rows.  Either destination may be null.
 struct UserReplayArgs {

@@ -70,15 +70,19 @@ struct UserProgramSpec {
   bool map = false;             // the optimiser (tda_user_maximize) in place of the kernels that sample: with `mala` over the source's
                                 // gradient (the MALA program's requirements), without it over differences of the step program's objective
   bool hmc = false;             // (with mala) the HMC program: tda_user_hmc_steps in place of tda_user_mala_steps, everything else the MALA program's
+  bool nuts = false;            // (with mala) the NUTS program: tda_user_nuts_steps in that place; the checkpoints of its trees are LDS behind the MALA program's
   bool operator==(const UserProgramSpec& o) const {
     return mala == o.mala && loglike_source == o.loglike_source && prior_form == o.prior_form && forward_wave == o.forward_wave &&
-           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave && replay == o.replay && qoi_form == o.qoi_form && map == o.map && hmc == o.hmc;
+           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave && replay == o.replay && qoi_form == o.qoi_form && map == o.map && hmc == o.hmc && nuts == o.nuts;
   }
 };
 
 // dynamic LDS of the MALA kernels: the sensitivity of the m outputs (s_sens[m] of tda_user_program.hip), and behind it the
 // outputs themselves under a likelihood that couples them
 inline size_t user_mala_lds(const UserProgramSpec& spec, int m) { return (spec.loglike_source && spec.loglike_wave ? 2 : 1) * (size_t)m * sizeof(double); }
+// dynamic LDS of tda_user_nuts_steps behind that: the U-turn checkpoints of a subtree, (momentum, running momentum sum) per row of
+// DP doubles, max_depth rows at the most
+inline size_t user_nuts_checkpoint_lds(int max_depth, int DP) { return 2 * (size_t)max_depth * (size_t)DP * sizeof(double); }
 // dynamic LDS of a program's kernels for m outputs: the MALA program's buffer, or the step program's s_out[m] under a wave form of
 // the model or of the likelihood (0 without one)
 inline size_t user_dynamic_lds(const UserProgramSpec& spec, int m) {
@@ -132,6 +136,7 @@ std::vector<const char*> user_program_options(const UserProgramSpec& s) {
   if (s.loglike_source && s.loglike_wave) opts.push_back("-DTDA_LOGLIKE_WAVE");  // (under MALA: tda_loglike_grad_wave too)
   if (s.mala) opts.push_back("-DTDA_USER_MALA");
   if (s.mala && s.hmc) opts.push_back("-DTDA_USER_HMC");
+  if (s.mala && s.nuts) opts.push_back("-DTDA_USER_NUTS");
   if (s.map) opts.push_back("-DTDA_USER_MAP");
   if (s.prior_form) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines the prior's gradient too)
   if (s.prior_form == 2) opts.push_back("-DTDA_PRIOR_WAVE");
@@ -185,10 +190,10 @@ UserBuildError diagnose_user_build(std::string log, const UserProgramSpec& spec,
   }
   for (const UserMissingRow& row : USER_MISSING)
     if ((row.applies & (spec.replay ? USER_REPLAY : spec.mala ? USER_MALA : USER_STEPS)) && log.find(row.tag) != std::string::npos)
-      return {row.code, std::string(spec.map && spec.mala ? "the optimiser over the source's gradient needs what MALA needs -- " : spec.mala && spec.hmc ? "HMC needs what MALA needs -- " : "") + row.message};
+      return {row.code, std::string(spec.map && spec.mala ? "the optimiser over the source's gradient needs what MALA needs -- " : spec.mala && spec.nuts ? "NUTS needs what MALA needs -- " : spec.mala && spec.hmc ? "HMC needs what MALA needs -- " : "") + row.message};
   if (log.size() > 400) log.resize(400);
   snprintf(buf, sizeof buf, "the forward-model source does not compile%s: %s",
-           spec.replay ? " with the replay kernel" : spec.map ? (spec.mala ? " with the optimiser over its gradient" : " with the optimiser") : spec.mala && spec.hmc ? " with the HMC kernels" : spec.mala ? " with the MALA kernels" : "",
+           spec.replay ? " with the replay kernel" : spec.map ? (spec.mala ? " with the optimiser over its gradient" : " with the optimiser") : spec.mala && spec.nuts ? " with the NUTS kernels" : spec.mala && spec.hmc ? " with the HMC kernels" : spec.mala ? " with the MALA kernels" : "",
            log.c_str());
   return {TDA_ERR_INVALID, buf};
 }

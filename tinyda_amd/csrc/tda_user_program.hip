@@ -62,6 +62,9 @@
 //   -DTDA_USER_HMC        (in addition to -DTDA_USER_MALA) the HMC kernel (tda_user_hmc_steps) in place of tda_user_mala_steps:
 //                         leapfrog trajectories on the log-posterior and gradient of the MALA program, whose requirements are its own;
 //                         tda_user_mala_grad0 stays and initialises the gradient
+// and one turns it into the NUTS program:
+//   -DTDA_USER_NUTS       (in addition to -DTDA_USER_MALA) the NUTS kernel (tda_user_nuts_steps) in that place: trees of leapfrog steps
+//                         that end at a U-turn, on the same log-posterior and gradient; tda_user_mala_grad0 stays as under HMC
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -613,7 +616,249 @@ __device__ __forceinline__ void tda_map_gradient(const UserMapArgs& a, const dou
 #endif
 }
 #else
-#ifdef TDA_USER_HMC
+#if defined(TDA_USER_NUTS)
+// The no-U-turn sampler in place of tda_user_mala_steps (the algorithm, step by step: include/tinyda_amd_nuts.h): multinomial NUTS
+// in iterative form, one wave per chain.  Both edges of the tree, its candidate, the new subtree's candidate, the moving leaf and
+// the two momentum sums stay in registers, two doubles per lane each; the log-posterior and its gradient are MALA's (the same
+// calls in the same order: tda_mala_outputs, the prior's three forms, tda_gradient / tda_gradient_wave), a leaf is one of HMC's
+// leapfrog steps.  The U-turn checkpoints of a subtree (momentum and running momentum sum at its even leaves) live in LDS behind
+// s_sens, because their index is a run-time value; every lane reads back only what it stored itself, so they need no barrier.
+// The kernel reads no variates but z: direction, merge and selection draws are Philox stream 8, computed here.
+// Every tree decision (finite log-posterior, divergence, selection, U-turn, merge) compares wave sums or Philox words, the same
+// bits in all 64 lanes, and goes through a scalar register: the wave leaves a loop as one, so every source function that may hold
+// a barrier or a shuffle is called from a converged wave.
+// Barriers: the one at the top of a leaf puts the readers of s_th / s_sens / s_grad of the leaf before it (of this subtree, of an
+// earlier one or of the previous step, whichever way they were left) behind it before the next position is stored.
+__device__ __forceinline__ void tda_nuts_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned& x, unsigned& y, unsigned& z) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1;
+    c3 = (unsigned)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  x = c0, y = c1, z = c2;
+}
+__device__ __forceinline__ double tda_nuts_u53(unsigned a, unsigned b) { return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0); }
+__device__ __forceinline__ double tda_nuts_logaddexp(double a, double b) {
+  const double hi = a > b ? a : b, lo = a > b ? b : a;
+  return hi + log1p(exp(lo - hi));
+}
+extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserNutsArgs a) {
+  extern __shared__ double s_sens[];  // [m] ([2 m] under TDA_LOGLIKE_WAVE), and at ck_off the checkpoints [max_depth][2][DP]
+  __shared__ double s_th[128];
+  TDA_DECLARE_WORK;
+#ifdef TDA_GRADIENT_WAVE
+  __shared__ double s_grad[128];
+#endif
+  const int lane = threadIdx.x, lane2 = lane + 64;
+  const long long c = blockIdx.x;
+  if (c >= a.N) return;
+  const bool lj = lane < a.d, lj2 = lane2 < a.d;
+  const size_t row = (size_t)c * a.DP;
+  double* const s_ck = s_sens + a.ck_off;
+  double cur = lj ? a.theta[row + lane] : 0.0, cur2 = lj2 ? a.theta[row + lane2] : 0.0;
+  double gc = lj ? a.grad[row + lane] : 0.0, gc2 = lj2 ? a.grad[row + lane2] : 0.0;
+  double lp = a.lp[c], ll = a.ll[c];
+  const double eps = a.scaling[c];
+  const double w = lj ? a.inv_mass[lane] : 1.0, w2 = lj2 ? a.inv_mass[lane2] : 1.0;
+  const double sw = sqrt(w), sw2 = sqrt(w2);
+  const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
+  const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
+  (void)pm, (void)pinv, (void)pm2, (void)pinv2;
+  const unsigned k0 = (unsigned)a.seed, k1 = (unsigned)(a.seed >> 32), gchain = (unsigned)(a.chain_offset + c);
+  double accsum = a.accsum[c];
+  long long n_leap = 0, n_div = 0, n_cap = 0, n_depth = 0;
+  int nacc = 0;
+  for (int s = 0; s < a.S; ++s) {
+    const double* z = a.inc + ((size_t)s * a.NP + c) * a.DP;
+    const unsigned gstep = (unsigned)(a.step0 + s);
+    const double p0 = lj ? z[lane] / sw : 0.0, p02 = lj2 ? z[lane2] / sw2 : 0.0;  // momentum ~ N(0, 1 / w)
+    const double h0 = -(lp + ll) + 0.5 * tda_wave_sum(w * (p0 * p0) + w2 * (p02 * p02));
+    // the tree: its edges (l: backward, r: forward), the sum of its momenta, its log-weight, its candidate
+    double lth = cur, lth2 = cur2, pl = p0, pl2 = p02, lg = gc, lg2 = gc2;
+    double rth = cur, rth2 = cur2, pr = p0, pr2 = p02, rg = gc, rg2 = gc2;
+    double rho = p0, rho2 = p02, LW = 0.0;
+    double cth = cur, cth2 = cur2, cg = gc, cg2 = gc2, clp = lp, cll = ll;
+    double asum = 0.0;
+    int moved = 0, nleaf = 0, depth = 0, stop = 0;  // stop: 1 a divergent leaf, 2 a U-turn inside the new subtree, 3 a U-turn of the whole tree
+    for (int j = 0; j < a.max_depth; ++j) {
+      unsigned x0, x1, x2;
+      tda_nuts_philox((unsigned)j, gstep, gchain, 8u, k0, k1, x0, x1, x2);
+      const int fwd = __builtin_amdgcn_readfirstlane((int)(x2 & 1u));
+      const double uj = tda_nuts_u53(x0, x1);
+      const double e = fwd ? eps : -eps, he = 0.5 * e;
+      double th = fwd ? rth : lth, th2 = fwd ? rth2 : lth2, p = fwd ? pr : pl, p2 = fwd ? pr2 : pl2, g = fwd ? rg : lg, g2 = fwd ? rg2 : lg2;
+      // the new subtree: its candidate, its log-weight, the sum of its momenta
+      double sth = 0.0, sth2 = 0.0, sg = 0.0, sg2 = 0.0, slp = 0.0, sll = 0.0, LWs = 0.0, rs = 0.0, rs2 = 0.0;
+      const int nl = 1 << j;
+      for (int n = 0; n < nl; ++n) {
+        p += he * g;
+        p2 += he * g2;
+        th += e * (w * p);  // (a lane without a parameter keeps p = 0 and th = 0)
+        th2 += e * (w2 * p2);
+        __syncthreads();
+        s_th[lane] = th;
+        s_th[lane2] = th2;
+        __syncthreads();
+        const double sum = tda_wave_sum(tda_mala_outputs(a, s_th, s_sens, s_work, lane));
+        const double ll_n = tda_loglike_of_sum(sum, a.w, a.var);
+        double lp_n;
+#if defined(TDA_PRIOR_SOURCE) && defined(TDA_PRIOR_WAVE)
+        lp_n = tda_wave_sum(tda_logprior_wave(s_th, a.d, a.pr_mean, a.pr_pinv, lane));
+#elif defined(TDA_PRIOR_SOURCE)
+        double pj = lj ? tda_logprior_term(th, pm, pinv, lane) : 0.0;
+        if (lj2) pj += tda_logprior_term(th2, pm2, pinv2, lane2);
+        lp_n = tda_wave_sum(pj);
+#else
+        double pj = 0.0;
+        if (lj) {
+          const double dv = th - pm;
+          pj = dv * dv * pinv;
+        }
+        if (lj2) {
+          const double dv2 = th2 - pm2;
+          pj += dv2 * dv2 * pinv2;
+        }
+        lp_n = -0.5 * (a.logconst + tda_wave_sum(pj));
+#endif
+        const double post_n = lp_n + ll_n;
+        nleaf += 1;
+        if (!__builtin_amdgcn_readfirstlane(__builtin_isfinite(post_n) ? 1 : 0)) {
+          stop = 1;
+          break;
+        }
+#ifdef TDA_GRADIENT_WAVE
+        s_grad[lane] = 0.0;  // (its readers of the previous leaf are behind the barriers above)
+        s_grad[lane2] = 0.0;
+#endif
+        __syncthreads();  // s_sens complete
+#ifdef TDA_GRADIENT_WAVE
+        tda_gradient_wave(s_th, a.d, s_sens, a.m, s_grad, s_work, lane);
+        __syncthreads();
+        g = lj ? TDA_PRIOR_GRAD(th, pm, pinv, lane) + s_grad[lane] : 0.0;
+        g2 = lj2 ? TDA_PRIOR_GRAD(th2, pm2, pinv2, lane2) + s_grad[lane2] : 0.0;
+#else
+        g = lj ? TDA_PRIOR_GRAD(th, pm, pinv, lane) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
+        g2 = lj2 ? TDA_PRIOR_GRAD(th2, pm2, pinv2, lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
+#endif
+        p += he * g;
+        p2 += he * g2;
+        // (a gradient that is not finite leaves a NaN momentum: the energy is NaN and the leaf divergent)
+        const double h = -post_n + 0.5 * tda_wave_sum(w * (p * p) + w2 * (p2 * p2));
+        if (__builtin_amdgcn_readfirstlane((h != h || h - h0 > 1000.0) ? 1 : 0)) {
+          stop = 1;
+          break;
+        }
+        const double lw = h0 - h, ew = exp(lw);
+        asum += ew < 1.0 ? ew : 1.0;
+        int take = 1;
+        if (n == 0) {
+          LWs = lw;
+          rs = p;
+          rs2 = p2;
+        } else {
+          LWs = tda_nuts_logaddexp(LWs, lw);
+          rs += p;
+          rs2 += p2;
+          tda_nuts_philox(32u + (unsigned)nleaf, gstep, gchain, 8u, k0, k1, x0, x1, x2);
+          take = __builtin_amdgcn_readfirstlane(tda_nuts_u53(x0, x1) < exp(lw - LWs) ? 1 : 0);
+        }
+        if (take) {
+          sth = th, sth2 = th2, sg = g, sg2 = g2, slp = lp_n, sll = ll_n;
+        }
+        // U-turns inside the subtree: leaf n closes the aligned sub-subtrees of 2^k leaves for k = 1 .. (trailing ones of n);
+        // the one of 2^k leaves began at the even leaf whose checkpoint is row popcount(n >> 1) - k + 1
+        const int top = __builtin_popcount((unsigned)n >> 1);
+        if (!(n & 1)) {
+          double* const ck = s_ck + (size_t)top * 2 * a.DP;
+          if (lj) ck[lane] = p, ck[a.DP + lane] = rs;
+          if (lj2) ck[lane2] = p2, ck[a.DP + lane2] = rs2;
+        } else {
+          const int low = top - __builtin_ctz(~(unsigned)n) + 1;
+          int turn = 0;
+          for (int k = top; k >= low; --k) {
+            const double* const ck = s_ck + (size_t)k * 2 * a.DP;
+            const double pa = lj ? ck[lane] : 0.0, pa2 = lj2 ? ck[lane2] : 0.0;
+            const double rr = lj ? (rs - ck[a.DP + lane]) + pa : 0.0, rr2 = lj2 ? (rs2 - ck[a.DP + lane2]) + pa2 : 0.0;
+            const double da = tda_wave_sum((w * pa) * rr + (w2 * pa2) * rr2), db = tda_wave_sum((w * p) * rr + (w2 * p2) * rr2);
+            turn |= (da > 0.0 && db > 0.0) ? 0 : 1;
+          }
+          if (__builtin_amdgcn_readfirstlane(turn)) {
+            stop = 2;
+            break;
+          }
+        }
+      }
+      if (stop) break;
+      // merge: the biased progressive rule on the candidates, the weights and the momentum sums, the extended edge
+      if (__builtin_amdgcn_readfirstlane(uj < exp(LWs - LW) ? 1 : 0)) {
+        cth = sth, cth2 = sth2, cg = sg, cg2 = sg2, clp = slp, cll = sll;
+        moved = 1;
+      }
+      LW = tda_nuts_logaddexp(LW, LWs);
+      rho += rs;
+      rho2 += rs2;
+      if (fwd) {
+        rth = th, rth2 = th2, pr = p, pr2 = p2, rg = g, rg2 = g2;
+      } else {
+        lth = th, lth2 = th2, pl = p, pl2 = p2, lg = g, lg2 = g2;
+      }
+      depth = j + 1;
+      const double da = tda_wave_sum((w * pl) * rho + (w2 * pl2) * rho2), db = tda_wave_sum((w * pr) * rho + (w2 * pr2) * rho2);
+      if (__builtin_amdgcn_readfirstlane((da > 0.0 && db > 0.0) ? 0 : 1)) {
+        stop = 3;
+        break;
+      }
+    }
+    cur = cth, cur2 = cth2, gc = cg, gc2 = cg2, lp = clp, ll = cll;
+    nacc += moved;
+    accsum += asum / (double)nleaf;
+    n_leap += nleaf;
+    n_div += stop == 1 ? 1 : 0;
+    n_cap += stop == 0 ? 1 : 0;
+    n_depth += depth;
+    const size_t r = (size_t)s * a.N + c;
+    if (lane == 0) {
+      if (a.rec_stats) {
+        a.rec_stats[r * 3 + 0] = lp;
+        a.rec_stats[r * 3 + 1] = ll;
+        a.rec_stats[r * 3 + 2] = lp + ll;
+      }
+      if (a.rec_acc) a.rec_acc[r] = (unsigned char)moved;
+    }
+    if (a.rec_params && lj) a.rec_params[r * a.d + lane] = cur;
+    if (a.rec_params && lj2) a.rec_params[r * a.d + lane2] = cur2;
+  }
+  if (lane < a.DP) {
+    a.theta[row + lane] = cur;
+    a.grad[row + lane] = gc;
+  }
+  if (lane2 < a.DP) {
+    a.theta[row + lane2] = cur2;
+    a.grad[row + lane2] = gc2;
+  }
+  if (lane == 0) {
+    a.lp[c] = lp;
+    a.ll[c] = ll;
+    if (a.acc_count) a.acc_count[c] += nacc;
+    if (a.scaling_out) {  // the engine's rule of the period boundary on the mean acceptance statistic
+      a.scaling_out[c] = exp(log(eps) + a.gamma_pow * (accsum / (double)a.period - a.alpha_star));
+      accsum = 0.0;
+    }
+    a.accsum[c] = accsum;
+    long long* const tot = a.totals + (size_t)c * TDA_NUTS_TOTALS;
+    tot[0] += n_leap;
+    tot[1] += n_div;
+    tot[2] += n_cap;
+    tot[3] += n_depth;
+  }
+}
+#elif defined(TDA_USER_HMC)
 // Hamiltonian Monte Carlo in place of tda_user_mala_steps: per step one momentum from the step's unit normals, n_leapfrog
 // leapfrog steps of size scaling[c] under the diagonal inverse mass w on the log-posterior and gradient that MALA evaluates
 // (the same calls in the same order: tda_mala_outputs, the prior's three forms, tda_gradient / tda_gradient_wave), one accept

@@ -6,7 +6,8 @@
 // This file is the host side only: compile, load, launch.  The program text (tda_user_program.hip) and the kernel-argument
 // structs (tda_user_args.h) are files of their own, embedded below as text; the user's source is the program's header
 // "tda_user_source.h".  The MALA kernels are a second program, compiled at init only when the proposal is MALA; under HMC the
-// HMC program (tda_user_hmc_steps beside tda_user_mala_grad0, the `hmc` flag of the build description) stands in its place.  What a build
+// HMC program (tda_user_hmc_steps beside tda_user_mala_grad0, the `hmc` flag of the build description) stands in its place, and under NUTS the
+// NUTS program (tda_user_nuts_steps, the `nuts` flag).  What a build
 // is made from without any HIP (the forms a source defines, the build key, the options, the reading of a failed compile) is
 // tda_user_build.h.
 #include <hip/hiprtc.h>
@@ -100,7 +101,7 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
     }
     return TDA_OK;
   }
-  HIP_TRY(hipModuleGetFunction(&out->steps, out->mod, mala ? (spec.hmc ? "tda_user_hmc_steps" : "tda_user_mala_steps") : "tda_user_steps"));
+  HIP_TRY(hipModuleGetFunction(&out->steps, out->mod, mala ? (spec.nuts ? "tda_user_nuts_steps" : spec.hmc ? "tda_user_hmc_steps" : "tda_user_mala_steps") : "tda_user_steps"));
   if (mala) {
     HIP_TRY(hipModuleGetFunction(&out->grad0, out->mod, "tda_user_mala_grad0"));
   } else {

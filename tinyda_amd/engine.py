@@ -110,7 +110,7 @@ class Engine:
 
     def set_proposal(self, kind, C_=None, scaling=1.0, adaptive=False, gamma=1.01, period=100, sd=None,
                      epsilon=1e-6, t0=0, block_moments=False, q_mean=None, state_operator=None, noise_operator=None, spectrum=None,
-                     n_leapfrog=None, inv_mass=None):
+                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8):
         Cm = None if C_ is None else _f64(C_)
         p = _lib.tda_proposal_params(C.sizeof(_lib.tda_proposal_params), kind, scaling, int(adaptive), period, gamma,
                                      _ptr(Cm), -1.0 if sd is None else sd, epsilon, t0, int(block_moments),
@@ -126,6 +126,8 @@ class Engine:
             self._ck(self.lib.tda_engine_set_proposal_spectrum(self.h, _ptr(V), _ptr(lam)))
         if n_leapfrog is not None:  # HMC (kind 7)
             self.set_hmc(n_leapfrog, inv_mass)
+        if max_depth is not None:  # NUTS (kind 8)
+            self.set_nuts(max_depth, target_accept, inv_mass)
 
     def set_hmc(self, n_leapfrog, inv_mass=None):
         """trajectory length and diagonal inverse mass (None: unit mass) of the HMC proposal: after set_proposal(7, ...), before init"""
@@ -133,6 +135,25 @@ class Engine:
         if w is not None and w.shape != (self.dim,):
             raise ValueError("inv_mass takes one positive value per parameter")
         self._ck(self.lib.tda_engine_set_hmc(self.h, int(n_leapfrog), _ptr(w)))
+
+    def set_nuts(self, max_depth, target_accept=0.8, inv_mass=None):
+        """tree depth (1 .. 10 doublings), the adaptation's target for the acceptance statistic and the diagonal inverse mass (None:
+        unit mass) of the NUTS proposal: after set_proposal(8, ...), before init"""
+        w = None if inv_mass is None else _f64(inv_mass)
+        if w is not None and w.shape != (self.dim,):
+            raise ValueError("inv_mass takes one positive value per parameter")
+        self._ck(self.lib.tda_engine_set_nuts(self.h, int(max_depth), float(target_accept), _ptr(w)))
+
+    def nuts_totals(self, out=None):
+        """per-chain totals of an initialised NUTS engine since init, [n_chains, 4] int64: leapfrog steps, divergent trees, trees at
+        max_depth, sum of tree depths.  out: a device tensor of that shape to copy into (nothing then crosses to the host)"""
+        if out is not None:
+            assert tuple(out.shape) == (self.n_chains, 4) and out.is_contiguous() and out.element_size() == 8
+            self._ck(self.lib.tda_engine_get_nuts_totals(self.h, out.data_ptr()))
+            return out
+        tot = np.empty((self.n_chains, 4), dtype=np.int64)
+        self._ck(self.lib.tda_engine_get_nuts_totals(self.h, tot.ctypes.data_as(C.c_void_p)))
+        return tot
 
     def set_prior_joint(self, kinds, loc, scale):
         """JointPrior of scalar components: kinds[j] 0 = norm(loc, scale), 1 = uniform(loc, scale); or 2 (_lib.PRIOR_SOURCE) for

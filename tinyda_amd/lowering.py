@@ -13,11 +13,11 @@ import numpy as np
 from . import _lib
 from ._contract import SIG
 from .likelihoods import _is_diagonal
-from .proposals import (DREAM, DREAMZ, HMC, MALA, AdaptiveMetropolis, CrankNicolson, GaussianRandomWalk, IndependenceSampler,
+from .proposals import (DREAM, DREAMZ, HMC, MALA, NUTS, AdaptiveMetropolis, CrankNicolson, GaussianRandomWalk, IndependenceSampler,
                         OperatorWeightedCrankNicolson)
 
 _GRW_PCN_AM = (GaussianRandomWalk, CrankNicolson, AdaptiveMetropolis)
-_DEVICE_PROPOSALS = _GRW_PCN_AM + (DREAMZ, DREAM, IndependenceSampler, OperatorWeightedCrankNicolson, MALA, HMC)
+_DEVICE_PROPOSALS = _GRW_PCN_AM + (DREAMZ, DREAM, IndependenceSampler, OperatorWeightedCrankNicolson, MALA, HMC, NUTS)
 
 MAX_LEVELS = 6  # (0.5; five and six levels: no error model, no dense observation covariance, at most 64 parameters -- MAX_LEVELS_FULL otherwise)
 MAX_LEVELS_FULL = 4
@@ -170,7 +170,7 @@ def _above_64_parameters(low, run):
     n, prop = run.n_levels, type(run.proposal)
     external = "batched" in low or "source" in low
     diagonal_error_model = n >= 2 and run.error_model is not None and run.diagonal_error_model
-    mala_on_source_gradient = prop in (MALA, HMC) and n == 1 and low.get("has_gradient")  # (a source-defined model's tda_gradient)
+    mala_on_source_gradient = prop in (MALA, HMC, NUTS) and n == 1 and low.get("has_gradient")  # (a source-defined model's tda_gradient)
     other_proposal = prop not in _GRW_PCN_AM and not mala_on_source_gradient
     other_model = (low.get("A") is None and not external) or "rosenbrock" in low  # (linear, source-defined and batched host models)
     dense_prior_of_external = external and not _is_diagonal(low["prior_cov"])  # (external models: diagonal prior covariance, as at any width)
@@ -287,7 +287,7 @@ def _mala(lows, run):
         if low["noise_kind"] not in _ISO_DIAG + (_lib.NOISE_SOURCE,) or np.asarray(low["data"]).shape[0] > 2048:
             return "%s over a source-defined model: isotropic or diagonal noise, at most 2048 outputs" % mala
     elif isinstance(run.proposal, HMC):  # (the engine's linear-model MALA, k_mh_steps with its closed-form gradient, has no leapfrog loop)
-        return "HMC: single level, a DeviceModel with tda_gradient, Gaussian prior with diagonal covariance or a DevicePrior with its gradient"
+        return "%s: single level, a DeviceModel with tda_gradient, Gaussian prior with diagonal covariance or a DevicePrior with its gradient" % mala
     elif run.n_levels != 1 or "source" in low or "batched" in low or "rosenbrock" in low or "prior_joint" in low:
         return "MALA: single level, linear model, Gaussian prior"
 

@@ -331,6 +331,132 @@ class HMC(MALA):
                     period=int(self.period), n_leapfrog=self.n_leapfrog, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
 
 
+def _logaddexp(a, b):
+    hi, lo = (a, b) if a > b else (b, a)
+    return hi + np.log1p(np.exp(lo - hi))
+
+
+class NUTS(HMC):
+    """The no-U-turn sampler (an extension: the reference has none): HMC whose trajectory length is chosen per step.  Multinomial
+    NUTS with the diagonal inverse mass w = `inv_mass` (None: 1) in iterative form, as include/tinyda_amd_nuts.h writes it out: a
+    tree of leapfrog steps of size `scaling` doubles forwards or backwards at random, at most `max_depth` times, until its ends
+    turn towards each other (or one inside the newest subtree does, or a leaf diverges: its energy error exceeds 1000 or its
+    log-posterior is not finite); the new state is drawn from the tree's leaves with weights exp(-energy error), biased towards
+    the newest subtree.  `accepted` is whether the state moved.  `adaptive` adapts the step size at the period boundary towards
+    `target_accept` in the mean of the leaves' min(1, exp(-energy error)).  On the device path (wherever HMC lowers) a whole tree
+    runs in one kernel, tda_user_nuts_steps; over any other model the host protocol below builds the same tree in NumPy, with the
+    momentum from np.random.standard_normal, the direction of a doubling from np.random.randint(2) and then its merge uniform
+    from np.random.random, and one np.random.random per leaf of a subtree after its first.  `totals` counts what the device's
+    proposal_state reports: n_leapfrog, n_divergent, n_max_depth, depth_sum."""
+
+    def __init__(self, scaling=0.1, max_depth=8, inv_mass=None, adaptive=False, target_accept=0.8, gamma=1.01, period=100):
+        if int(max_depth) != max_depth or not 1 <= max_depth <= 10:
+            raise ValueError("max_depth must be an integer in 1 .. 10, not %r" % (max_depth,))
+        if not 0.0 < target_accept < 1.0:
+            raise ValueError("target_accept must lie in (0, 1), not %r" % (target_accept,))
+        super().__init__(scaling, 1, inv_mass, adaptive, gamma, period)
+        self.n_leapfrog = None  # (chosen per step)
+        self.max_depth, self.target_accept = int(max_depth), float(target_accept)
+        self.alpha_star = self.target_accept
+        self.totals = dict(n_leapfrog=0, n_divergent=0, n_max_depth=0, depth_sum=0)
+        self._stat, self._stat_sum = 0.0, 0.0
+
+    def make_proposal(self, link):
+        if not hasattr(link, "gradient"):
+            link.gradient = self.compute_gradient(link)
+        eps, w = self.scaling, np.ones(self.d) if self.inv_mass is None else self.inv_mass
+        theta0 = np.asarray(link.parameters, dtype=np.float64)
+        p0 = np.random.standard_normal(self.d) / np.sqrt(w)
+        h0 = -link.posterior + 0.5 * np.sum(w * (p0 * p0))
+        left = right = (theta0, p0, np.asarray(link.gradient, dtype=np.float64))
+        rho, LW = p0, 0.0
+        cand = (theta0, left[2], 0)  # (position, gradient, the number of the leaf in this step; 0: the initial state)
+        asum, nleaf, depth, stop = 0.0, 0, 0, None
+        with np.errstate(all="ignore"):
+            for j in range(self.max_depth):
+                fwd, uj = int(np.random.randint(2)), np.random.random()
+                e = eps if fwd else -eps
+                theta, p, g = right if fwd else left
+                ck, sub, LWs, rs = {}, None, 0.0, None
+                for n in range(1 << j):
+                    p = p + (0.5 * e) * g
+                    theta = theta + e * (w * p)
+                    at = self.posterior.create_link(theta)
+                    nleaf += 1
+                    if not np.isfinite(at.posterior):
+                        stop = "divergent"
+                        break
+                    g = np.asarray(self.compute_gradient(at), dtype=np.float64)
+                    p = p + (0.5 * e) * g
+                    h = -at.posterior + 0.5 * np.sum(w * (p * p))
+                    if np.isnan(h) or h - h0 > 1000.0:
+                        stop = "divergent"
+                        break
+                    lw = h0 - h
+                    asum += min(1.0, np.exp(lw))
+                    if n == 0:
+                        LWs, rs, sub = lw, p, (theta, g, nleaf)
+                    else:
+                        LWs, rs = _logaddexp(LWs, lw), rs + p
+                        if np.random.random() < np.exp(lw - LWs):
+                            sub = (theta, g, nleaf)
+                    top = bin(n >> 1).count("1")
+                    if n % 2 == 0:
+                        ck[top] = (p, rs)
+                    else:
+                        ones, turn = (n ^ (n + 1)).bit_length() - 1, False  # trailing one bits of n
+                        for k in range(top, top - ones, -1):
+                            pa, ra = ck[k]
+                            rr = (rs - ra) + pa
+                            if not (np.sum((w * pa) * rr) > 0.0 and np.sum((w * p) * rr) > 0.0):
+                                turn = True
+                        if turn:
+                            stop = "uturn_subtree"
+                            break
+                if stop:
+                    break
+                if uj < np.exp(LWs - LW):
+                    cand = sub
+                LW, rho = _logaddexp(LW, LWs), rho + rs
+                if fwd:
+                    right = (theta, p, g)
+                else:
+                    left = (theta, p, g)
+                depth = j + 1
+                if not (np.sum((w * left[1]) * rho) > 0.0 and np.sum((w * right[1]) * rho) > 0.0):
+                    stop = "uturn_tree"
+                    break
+        self._stat = asum / nleaf
+        self._end = cand
+        self.last_tree = dict(stop=stop or "max_depth", depth=depth, n_leapfrog=nleaf, selected=cand[2], stat=self._stat)
+        self.totals["n_leapfrog"] += nleaf
+        self.totals["n_divergent"] += stop == "divergent"
+        self.totals["n_max_depth"] += stop is None
+        self.totals["depth_sum"] += depth
+        return cand[0]
+
+    def get_acceptance(self, proposal_link, previous_link):
+        end = getattr(self, "_end", None)
+        if end is None or end[2] == 0 or (end[0] is not proposal_link.parameters and not np.array_equal(end[0], proposal_link.parameters)):
+            return 0.0
+        proposal_link.gradient = end[1]
+        return 1.0
+
+    def adapt(self, **kwargs):
+        self.t += 1
+        self._stat_sum += self._stat
+        if self.t % self.period == 0:
+            if self.adaptive:
+                self.scaling = np.exp(np.log(self.scaling) + self.gamma ** -self.k * (self._stat_sum / self.period - self.alpha_star))
+                self.k += 1
+            self._stat_sum = 0.0
+
+    def _lowering(self):
+        return dict(kind=_lib.PROP_NUTS, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
+                    period=int(self.period), max_depth=self.max_depth, target_accept=self.target_accept,
+                    inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+
+
 class AdaptiveMetropolis(GaussianRandomWalk):
     """Haario et al. (2001): proposal covariance <- running sample covariance every `period` adapt calls
     once t >= t0 (proposal.py:372-512).
