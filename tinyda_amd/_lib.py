@@ -214,6 +214,12 @@ NUTS_SYMBOLS = {
     "tda_engine_get_nuts_totals": (C.c_int, [_P, _P]),
 }
 
+# every symbol include/tinyda_amd_mass.h declares: bound by load() only (the CPU build of the ABI has neither HMC nor NUTS)
+MASS_SYMBOLS = {
+    "tda_engine_set_mass_adaptation": (C.c_int, [_P, C.c_int64]),
+    "tda_engine_get_mass": (C.c_int, [_P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -255,7 +261,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # missing ROCm runtime etc.
         raise EngineError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()) + list(NUTS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()) + list(NUTS_SYMBOLS.items()) + list(MASS_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

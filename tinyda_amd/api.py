@@ -155,6 +155,10 @@ def sample(posteriors, proposal, iterations, n_chains=1, initial_parameters=None
     if distributed:
         from . import distributed as tdist
 
+        # refused here, on every rank alike, before any rank waits for another (the rule and its reason: lowering._mass_adaptation)
+        why = lower([], proposal, distributed=True)[1] if getattr(proposal, "adapt_mass", 0) else None
+        if why is not None and "adapt_mass" in why:
+            raise ValueError("tinyda_amd.sample: " + why)
         one_gpu = os.environ.get("TINYDA_BENCH_ONE_GPU") == "1"  # rehearsal of the N > 1 path on a one-GPU box: every rank on cuda:0, gloo
         rank, local_rank, world = tdist.init_process_group("gloo" if one_gpu else None)
         total = n_chains
@@ -223,7 +227,7 @@ def sample(posteriors, proposal, iterations, n_chains=1, initial_parameters=None
     if diag_aem and adaptive_error_model != "state-independent":
         raise ValueError("the diagonal error model is state-independent")
     plan, why = (None, None) if backend == "host" else lower(posteriors, proposal, diag_aem, adaptive_error_model if n_levels > 1 else None,
-                                                             bool(randomize_subchain_length) and n_levels > 1)
+                                                             bool(randomize_subchain_length) and n_levels > 1, bool(distributed))
     if plan is not None and isinstance(proposal, DREAMZ) and n_levels > 1 and diag_aem:
         # (DREAMZ below a hierarchy runs with the reference's dense error model; the diagonal extension: host protocol)
         plan, why = None, "DREAMZ below a hierarchy runs with the dense error model on the device, not the diagonal extension"
@@ -354,26 +358,40 @@ class LazyProposalState(Mapping):
     """result['proposal_state'] of a device run: the final state of the proposal (scaling, covariance C, AdaptiveMetropolis
     moments, counters) -- read from the device when first indexed.  The engine hands its proposal buffers over without a copy
     (tda_engine_detach_proposal_state) and is gone by the time sample() returns; unpacking 4096 covariance matrices took three
-    times as long as the 2000 iterations that produced them, and hardly any caller looks at them."""
+    times as long as the 2000 iterations that produced them, and hardly any caller looks at them.
+    After an HMC / NUTS run with adapt_mass > 0 (`with_mass`) it also holds `inv_mass` ([dim], the mass in force: copied out of the
+    engine into device memory before it closes, read when the state is first indexed), `mass_updates` (window ends applied) and
+    `mass_refused` (entries that a window end left unchanged)."""
+
+    _MASS_KEYS = ("inv_mass", "mass_updates", "mass_refused")
 
     def __init__(self, snapshot, n_chains, dim, want_am):
         self._snap, self._shape, self._want_am, self._data = snapshot, (n_chains, dim), want_am, None
+        self._mass, self._has_mass = None, False
+
+    def with_mass(self, inv_mass, info):
+        self._mass, self._has_mass = (inv_mass, info), True
+        return self
 
     def _load(self):
         if self._data is None:
             self._data = self._snap.read(self._shape[0], self._shape[1], self._want_am)
             self._snap.close()
             self._snap = None
+            if self._mass is not None:
+                w, info = self._mass
+                self._data = dict(self._data, inv_mass=w.cpu().numpy(), mass_updates=info["updates"], mass_refused=info["refused"])
+                self._mass = None
         return self._data
 
     def __getitem__(self, key):
         return self._load()[key]
 
     def __iter__(self):
-        return iter(("scaling", "C", "am_mu", "am_sigma", "t", "k"))
+        return iter(("scaling", "C", "am_mu", "am_sigma", "t", "k") + (self._MASS_KEYS if self._has_mass else ()))
 
     def __len__(self):
-        return 6
+        return 6 + (3 if self._has_mass else 0)
 
     # pickle / copy: the snapshot is a ctypes handle (not picklable, and a shallow copy would free it twice) -- a copy of any
     # kind is the materialised state, a plain dict of arrays, as the reference's result dict is plain Python
@@ -417,10 +435,9 @@ class NutsProposalState(LazyProposalState):
 def _materialised_proposal_state(data, shape, want_am):
     if "n_leapfrog" in data:
         st = NutsProposalState(None, shape[0], shape[1], None, 0)
-        st._data = data
-        return st
-    st = LazyProposalState(None, shape[0], shape[1], want_am)
-    st._data = data
+    else:
+        st = LazyProposalState(None, shape[0], shape[1], want_am)
+    st._data, st._has_mass = data, "inv_mass" in data
     return st
 
 
@@ -485,6 +502,14 @@ def _configure_engine(eng, plan, prior, initial_parameters, chain_offset, seed, 
     eng.init(None if initial_parameters is None else np.stack([np.asarray(p, float) for p in initial_parameters]))
 
 
+def _mass_of(eng, prop, torch, tdev):
+    """(the inverse mass as a device tensor, the adaptation's counters) of a run with adapt_mass > 0; None otherwise"""
+    if not prop.get("adapt_mass"):
+        return None
+    with torch.cuda.device(tdev):
+        return eng.get_mass(torch.empty((eng.dim,), dtype=torch.float64, device=tdev))
+
+
 def _sample_device(plan, posterior, iterations, n_chains, initial_parameters, seed, device, chain_offset,
                    distributed=False, total_chains=None, overlap_exchange=False, peer_archive=False, thin=1, progress=False):
     from .engine import Engine  # raises EngineError when libtinyda_hip.so is missing: no CPU fallback
@@ -545,9 +570,13 @@ def _sample_device(plan, posterior, iterations, n_chains, initial_parameters, se
         elif prop["kind"] == _lib.PROP_NUTS:
             with torch.cuda.device(tdev):
                 totals = eng.nuts_totals(torch.empty((N, 4), dtype=torch.int64, device=tdev))
+            mass = _mass_of(eng, prop, torch, tdev)
             state = NutsProposalState(eng.detach_proposal_state(), N, d, totals, T)
         else:
+            mass = _mass_of(eng, prop, torch, tdev)
             state = LazyProposalState(eng.detach_proposal_state(), N, d, prop["kind"] == _lib.PROP_AM)
+        if prop["kind"] != _lib.PROP_DREAMZ and mass is not None:
+            state.with_mass(*mass)
     finally:
         eng.close()
     result = {"sampler": "MH", "n_chains": n_chains, "iterations": R + 1, "backend": "hip",

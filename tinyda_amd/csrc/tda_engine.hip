@@ -368,6 +368,12 @@ struct tda_engine {
   double nuts_target = 0.8;
   DevBuf<double> nuts_accsum;      // [NP]: the running period's sum of acceptance statistics
   DevBuf<long long> nuts_totals;   // [NP][TDA_NUTS_TOTALS]
+  // warm-up adaptation of the mass above (tda_engine_set_mass_adaptation, tda_host_mass.inc): state of a mass-adapting engine alone
+  int64_t mass_W = 0;        // warm-up steps; 0: off
+  int64_t mass_n = 0;        // steps folded into the running window
+  int64_t mass_updates = 0;  // window ends applied
+  DevBuf<double> mass_mean, mass_M2;  // [NP][DP]: the chains' running moments of the window
+  DevBuf<unsigned int> mass_refused;  // [1]: entries that a window's end left unchanged
   DevBuf<double> q_mean_d, lq, qzblk, qzblk2[2];
   double am_sd = 1.0;
   bool L_shared = true;
@@ -1410,6 +1416,7 @@ int64_t tda_release_cached_memory(void) { return (int64_t)g_pool.trim(); }
 }  // extern "C"
 
 // ---- the rest of the ABI, by family (textual includes: one translation unit) ----
+#include "tda_host_mass.inc"
 #include "tda_host_setup.inc"
 #include "tda_host_dreamz_archive.inc"
 #include "tda_host_state.inc"

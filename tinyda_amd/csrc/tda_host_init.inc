@@ -310,6 +310,18 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       for (int j = 0; j < d && !e->hmc_inv_mass_h.empty(); ++j) wm[j] = e->hmc_inv_mass_h[j];
       if ((rc = e->hmc_inv_mass.upload(wm))) return rc;
     }
+    e->mass_n = 0;
+    e->mass_updates = 0;
+    if (leapfrog_proposal(e->pp.kind) && e->mass_W > 0) {  // the window's moments: state of a mass-adapting engine alone
+      if ((rc = e->mass_mean.alloc((size_t)NP * DP)) || (rc = e->mass_M2.alloc((size_t)NP * DP)) || (rc = e->mass_refused.alloc(1))) return rc;
+      HIP_TRY(hipMemsetAsync(e->mass_mean.p, 0, (size_t)NP * DP * sizeof(double), e->stream));
+      HIP_TRY(hipMemsetAsync(e->mass_M2.p, 0, (size_t)NP * DP * sizeof(double), e->stream));
+      HIP_TRY(hipMemsetAsync(e->mass_refused.p, 0, sizeof(unsigned int), e->stream));
+    } else {
+      e->mass_mean.release();
+      e->mass_M2.release();
+      e->mass_refused.release();
+    }
   } else if (mala) {
     // linear model: gradient of the log-posterior of the linear-Gaussian target (proposal.py:986-998; utils.py:273-287) in
     // closed form, grad = c - H theta with

@@ -181,7 +181,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
   }
   auto block_len = [&](int64_t t_now, int64_t left) {
     int64_t S = std::min<int64_t>(left, e->SMAX);
-    if (periodic) S = std::min<int64_t>(S, period - (t_now % period));
+    if (periodic || mass_warming(e, t_now)) S = std::min<int64_t>(S, period - (t_now % period));  // (a window of the mass adaptation ends with a block)
     return S;
   };
   // draw block `blk` (steps t0 .. t0 + S - 1, the exp_off-th exported step) into buffer blk & 1 on the rng stream
@@ -326,7 +326,8 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     double* const blk_stats = (async_host && (blk & 1)) ? e->rec_stats2.p : e->rec_stats.p;
     uint8_t* const blk_acc = (async_host && (blk & 1)) ? e->rec_acc2.p : e->rec_acc.p;
     if (async_host && blk >= 2) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_cp[blk & 1], 0));  // buffer set free again
-    sa.rec_params = (p_dev && thin == 1) ? o_params + (size_t)done * N * d : ((o_params || is_am) ? blk_params : nullptr);
+    // (the same while the mass of HMC / NUTS adapts: k_mass_accumulate reads every state of the block)
+    sa.rec_params = (p_dev && thin == 1) ? o_params + (size_t)done * N * d : ((o_params || is_am || mass_warming(e, e->t)) ? blk_params : nullptr);
     sa.rec_stats = (s_dev && thin == 1) ? o_stats + (size_t)done * N * 3 : (o_stats ? blk_stats : nullptr);
     sa.rec_acc = (a_dev && thin == 1) ? o_acc + (size_t)done * N : ((o_acc || (e->prog_h && thin > 1)) ? blk_acc : nullptr);
     const bool user_stepwise = lv.model == MODEL_USER && (lv.noise_kind == TDA_NOISE_DENSE || e->pp.kind == TDA_PROP_INDEPENDENCE || e->pp.kind == TDA_PROP_OWCN);
@@ -497,6 +498,7 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     }
     HIP_TRY(hipGetLastError());
     if (boundary && adaptive) e->k_adapt += 1;
+    if (int mrc = mass_after_block(e, e->t, S, sa.rec_params)) return mrc;  // (warm-up adaptation of the mass: tda_host_mass.inc)
 
     // ---- progress mark; thinned / host-side records ----
     int rc;

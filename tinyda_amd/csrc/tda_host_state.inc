@@ -65,6 +65,7 @@ struct StateItem {
   void* p;
   size_t bytes;
   bool device;
+  bool check = false;  // a host item that set_state compares with the engine's own value and refuses on a difference
 };
 
 // every piece of mutable state of an initialised engine, in a fixed order for its configuration
@@ -91,6 +92,16 @@ void enumerate_state(tda_engine* e, std::vector<StateItem>& v) {
   dev(e->mala_grad);
   dev(e->nuts_accsum);  // (a NUTS engine alone holds these two: the running period's acceptance sum and the per-chain totals)
   dev(e->nuts_totals);
+  if (e->mass_W > 0 && e->mass_mean.p) {  // a mass-adapting HMC / NUTS engine alone (tinyda_amd_mass.h)
+    v.push_back({&e->mass_W, sizeof e->mass_W, false, true});  // (checked, not adopted: the schedule is the engine's configuration)
+    v.push_back({&e->pp.period, sizeof e->pp.period, false, true});
+    host(&e->mass_n, sizeof e->mass_n);
+    host(&e->mass_updates, sizeof e->mass_updates);
+    dev(e->hmc_inv_mass);
+    dev(e->mass_mean);
+    dev(e->mass_M2);
+    dev(e->mass_refused);
+  }
   if (e->nlev > 1) {
     host(e->cnt, sizeof e->cnt);
     host(e->done, sizeof e->done);
@@ -212,11 +223,26 @@ int tda_engine_set_state(tda_engine* e, const void* blob, int64_t bytes) {
     if (thin_saved != thin_now)
       return fail(TDA_ERR_INVALID, "state blob was saved with record thinning %d, this engine is set to %d", thin_saved, thin_now);
   }
+  {  // the checked items first, so that a refused blob leaves the engine as it was
+    const char* q = o;
+    for (auto& it : v) {
+      uint64_t b;
+      memcpy(&b, q, 8);
+      if (b != it.bytes) return fail(TDA_ERR_INVALID, "state blob layout mismatch");
+      if (it.check && memcmp(it.p, q + 8, it.bytes) != 0)
+        return fail(TDA_ERR_INVALID, "state blob was saved under another mass adaptation (warm-up steps or period differ from this engine's)");
+      q += 8 + b;
+    }
+  }
   for (auto& it : v) {
     uint64_t b;
     memcpy(&b, o, 8);
     if (b != it.bytes) return fail(TDA_ERR_INVALID, "state blob layout mismatch");
     o += 8;
+    if (it.check) {
+      o += it.bytes;
+      continue;
+    }
     if (it.device) HIP_TRY(hipMemcpy(it.p, o, it.bytes, hipMemcpyHostToDevice));
     else memcpy(it.p, o, it.bytes);
     o += it.bytes;

@@ -110,7 +110,7 @@ class Engine:
 
     def set_proposal(self, kind, C_=None, scaling=1.0, adaptive=False, gamma=1.01, period=100, sd=None,
                      epsilon=1e-6, t0=0, block_moments=False, q_mean=None, state_operator=None, noise_operator=None, spectrum=None,
-                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8):
+                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8, adapt_mass=0):
         Cm = None if C_ is None else _f64(C_)
         p = _lib.tda_proposal_params(C.sizeof(_lib.tda_proposal_params), kind, scaling, int(adaptive), period, gamma,
                                      _ptr(Cm), -1.0 if sd is None else sd, epsilon, t0, int(block_moments),
@@ -128,6 +128,26 @@ class Engine:
             self.set_hmc(n_leapfrog, inv_mass)
         if max_depth is not None:  # NUTS (kind 8)
             self.set_nuts(max_depth, target_accept, inv_mass)
+        if adapt_mass:  # HMC / NUTS: warm-up adaptation of the mass
+            self.set_mass_adaptation(adapt_mass)
+
+    def set_mass_adaptation(self, warmup_steps):
+        """adapt the diagonal inverse mass of HMC / NUTS during the first `warmup_steps` steps, pooled over the engine's chains
+        (include/tinyda_amd_mass.h): a multiple of the period, at least two periods, 0: off.  After set_proposal, before init"""
+        self._ck(self.lib.tda_engine_set_mass_adaptation(self.h, int(warmup_steps)))
+
+    def get_mass(self, out=None):
+        """(inv_mass [dim], info) of an initialised HMC / NUTS engine: the mass in force, and info = dict(updates, window_steps,
+        next_update (global step, -1: none), refused).  out: a device tensor [dim] to copy the mass into instead"""
+        info = np.zeros(4, dtype=np.int64)
+        if out is not None:
+            assert tuple(out.shape) == (self.dim,) and out.is_contiguous() and out.element_size() == 8
+            w = out
+            self._ck(self.lib.tda_engine_get_mass(self.h, out.data_ptr(), _ptr(info)))
+        else:
+            w = np.empty(self.dim)
+            self._ck(self.lib.tda_engine_get_mass(self.h, _ptr(w), _ptr(info)))
+        return w, dict(updates=int(info[0]), window_steps=int(info[1]), next_update=int(info[2]), refused=int(info[3]))
 
     def set_hmc(self, n_leapfrog, inv_mass=None):
         """trajectory length and diagonal inverse mass (None: unit mass) of the HMC proposal: after set_proposal(7, ...), before init"""

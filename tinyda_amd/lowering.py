@@ -28,14 +28,14 @@ MAX_AEM_OUTPUTS_HOST_SEQUENCED = 256  # (the same since k_ext_aem_*<256>)
 _ISO_DIAG = (_lib.NOISE_ISO, _lib.NOISE_DIAG)
 
 # the run's options: sample()'s adaptive_error_model after its own validation (None / 'state-independent' / 'state-dependent'),
-# whether it is the diagonal extension, and randomize_subchain_length
-Run = namedtuple("Run", "n_levels proposal error_model diagonal_error_model randomize")
+# whether it is the diagonal extension, randomize_subchain_length, and whether the chains are sharded over processes
+Run = namedtuple("Run", "n_levels proposal error_model diagonal_error_model randomize distributed")
 
 
-def lower(posteriors, proposal, diagonal_error_model=False, error_model=None, randomize=False):
+def lower(posteriors, proposal, diagonal_error_model=False, error_model=None, randomize=False, distributed=False):
     """-> ((level descriptions, proposal description), None), or (None, the first reason why not)"""
-    run = Run(len(posteriors), proposal, error_model, diagonal_error_model, randomize)
-    why = _hierarchy_size(run)
+    run = Run(len(posteriors), proposal, error_model, diagonal_error_model, randomize, distributed)
+    why = _mass_adaptation(run) or _hierarchy_size(run)
     lows = []
     for post in posteriors:
         if why is None:
@@ -53,6 +53,14 @@ def lower(posteriors, proposal, diagonal_error_model=False, error_model=None, ra
     if prop is None:  # an option of a lowerable proposal class that the engine does not know: host protocol under 'auto'
         return None, "an option of %s the engine does not implement" % type(proposal).__name__
     return (lows, prop), None
+
+
+# adapt_mass of HMC / NUTS pools the variances over the chains of ONE engine (include/tinyda_amd_mass.h): under
+# distributed=True every rank would learn a mass of its own, and the union over ranks would no longer be a single-process run
+def _mass_adaptation(run):
+    if run.distributed and getattr(run.proposal, "adapt_mass", 0):
+        return ("adapt_mass = %d of %s under distributed=True: the mass is pooled over the chains of one process only"
+                % (run.proposal.adapt_mass, type(run.proposal).__name__))
 
 
 def _hierarchy_size(run):

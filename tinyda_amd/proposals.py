@@ -269,6 +269,48 @@ class MALA(GaussianRandomWalk):
                     gamma=float(self.gamma), period=int(self.period))
 
 
+def mass_windows(W, period):
+    """The windows of the warm-up adaptation of the mass (include/tinyda_amd_mass.h, "Schedule"), as (first step, last step
+    exclusive) with steps counted from 0: W steps of P = W / period periods; period 0 is a buffer, windows of 1, 2, 4, ...
+    periods follow, and a window of L periods starting at period s with s + 3 L > P takes all the rest and is the last."""
+    if int(W) != W or int(period) != period or period < 1 or W % period != 0 or W < 2 * period:
+        raise ValueError("adapt_mass = %r must be a multiple of the period (%r) and at least two periods (or 0: off)" % (W, period))
+    W, period = int(W), int(period)
+    P, out, s, L = W // period, [], 1, 1
+    while s < P:
+        if s + 3 * L > P:
+            L = P - s
+        out.append((s * period, (s + L) * period))
+        s, L = s + L, 2 * L
+    return out
+
+
+def _mass_pool(mean, M2, n, inv_mass):
+    """The window's end of include/tinyda_amd_mass.h ("Update") over the moments mean, M2 [N, d] of N chains with n states each:
+    -> (the new inverse mass, the number of entries refused).  Sums in the kernel's order: 256 strided partial sums, then a tree."""
+    N = mean.shape[0]
+
+    def pooled(x):
+        part = np.zeros((256, x.shape[1]))
+        for r in range(0, N, 256):
+            part[:min(256, N - r)] += x[r:r + 256]
+        s = 128
+        while s >= 1:
+            part[:s] += part[s:2 * s]
+            s >>= 1
+        return part[0]
+
+    with np.errstate(all="ignore"):
+        mbar = pooled(mean) / float(N)
+        dm = mean - mbar[None, :]
+        B, Wn = pooled(dm * dm), pooled(M2)
+        T = float(n) * float(N)
+        var = (Wn + float(n) * B) / (T - 1.0)
+        w = var * T / (T + 5.0) + 1e-3 * 5.0 / (T + 5.0)
+        ok = np.isfinite(w) & (w > 0.0)
+    return np.where(ok, w, inv_mass), int(np.sum(~ok))
+
+
 class HMC(MALA):
     """Hamiltonian Monte Carlo (an extension: the reference has none): per proposal a momentum p = z / sqrt(w) from d unit normals
     z, `n_leapfrog` leapfrog steps of size `scaling` under the diagonal inverse mass w = `inv_mass` (None: 1) on the log-posterior
@@ -276,11 +318,19 @@ class HMC(MALA):
     difference, alpha = exp(post' - post + K0 - K1) with K = 1/2 sum_j w_j p_j^2.  A position whose log-posterior is NaN or infinite
     ends the trajectory and rejects.  With one step and unit mass this is MALA.  `adaptive` adapts the step size towards 0.65
     acceptance.  On the device path (a single-level DeviceModel with `tda_gradient`, wherever MALA lowers) the whole trajectory
-    runs in one kernel, tda_user_hmc_steps; over any other model the host protocol below runs."""
+    runs in one kernel, tda_user_hmc_steps; over any other model the host protocol below runs.
+
+    `adapt_mass` = W > 0 adapts the inverse mass during the first W steps (a multiple of `period`, at least two periods), from
+    `inv_mass` as the starting mass, as include/tinyda_amd_mass.h writes it out: regularised variances of the states of windows
+    that double in length (`mass_windows`), after which the mass is frozen; with `adaptive` (recommended) the step size's
+    diminishing gain restarts at every update of the mass.  On the device path the variances are pooled over all chains of the
+    engine, which share one mass vector.  On the host path every chain has its own copy of the proposal and adapts from its own
+    window alone, on the same schedule, with the same regulariser and the same restart: pooling over chains exists only on the
+    device.  `mass_updates` and `mass_refused` count the window ends applied and the entries they left unchanged."""
 
     alpha_star = 0.65
 
-    def __init__(self, scaling=0.1, n_leapfrog=8, inv_mass=None, adaptive=False, gamma=1.01, period=100):
+    def __init__(self, scaling=0.1, n_leapfrog=8, inv_mass=None, adaptive=False, gamma=1.01, period=100, adapt_mass=0):
         if int(n_leapfrog) != n_leapfrog or not 1 <= n_leapfrog <= 1024:
             raise ValueError("n_leapfrog must be an integer in 1 .. 1024, not %r" % (n_leapfrog,))
         if inv_mass is not None:
@@ -289,11 +339,46 @@ class HMC(MALA):
                 raise ValueError("inv_mass takes one finite, positive value per parameter")
         self.n_leapfrog, self.inv_mass = int(n_leapfrog), inv_mass
         self._init_scaling(scaling, adaptive, gamma, period)
+        if adapt_mass != 0 and (int(adapt_mass) != adapt_mass or adapt_mass < 0):
+            raise ValueError("adapt_mass = %r must be a multiple of the period (%r) and at least two periods (or 0: off)" % (adapt_mass, period))
+        self.adapt_mass = int(adapt_mass)
+        self._mass_windows = mass_windows(self.adapt_mass, period) if self.adapt_mass else []
+        self._mass_n, self._mass_mean, self._mass_M2 = 0, None, None
+        self.mass_updates, self.mass_refused = 0, 0
 
     def setup_proposal(self, **kwargs):
         super().setup_proposal(**kwargs)
         if self.inv_mass is not None and self.inv_mass.shape != (self.d,):
             raise ValueError("inv_mass has %d entries for %d parameters" % (self.inv_mass.shape[0], self.d))
+        if self.adapt_mass and self.inv_mass is None:
+            self.inv_mass = np.ones(self.d)
+
+    def _adapt_mass(self, x):
+        """fold the state of step self.t - 1 (steps counted from 0) into its window; at the window's end the new mass"""
+        s = self.t - 1
+        if s >= self.adapt_mass:
+            return
+        for first, end in self._mass_windows:
+            if first <= s < end:
+                x = np.asarray(x, dtype=np.float64)
+                if self._mass_n == 0:
+                    self._mass_mean, self._mass_M2 = np.zeros(self.d), np.zeros(self.d)
+                self._mass_n += 1
+                delta = x - self._mass_mean
+                self._mass_mean = self._mass_mean + delta / float(self._mass_n)
+                self._mass_M2 = self._mass_M2 + delta * (x - self._mass_mean)
+                if s + 1 == end:
+                    self.inv_mass, refused = _mass_pool(self._mass_mean[None, :], self._mass_M2[None, :], self._mass_n, self.inv_mass)
+                    self.mass_refused += refused
+                    self.mass_updates += 1
+                    self._mass_n = 0
+                    if self.adaptive:
+                        self.k = 0  # the step-size rule's gain is full again under the new metric
+
+    def adapt(self, **kwargs):
+        super().adapt(**kwargs)
+        if self.adapt_mass:
+            self._adapt_mass(kwargs["parameters"])
 
     def make_proposal(self, link):
         if not hasattr(link, "gradient"):
@@ -327,8 +412,9 @@ class HMC(MALA):
         return 0.0
 
     def _lowering(self):
-        return dict(kind=_lib.PROP_HMC, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
-                    period=int(self.period), n_leapfrog=self.n_leapfrog, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+        low = dict(kind=_lib.PROP_HMC, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
+                   period=int(self.period), n_leapfrog=self.n_leapfrog, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+        return dict(low, adapt_mass=self.adapt_mass) if self.adapt_mass else low  # (off: the plan is what it was)
 
 
 def _logaddexp(a, b):
@@ -347,14 +433,15 @@ class NUTS(HMC):
     runs in one kernel, tda_user_nuts_steps; over any other model the host protocol below builds the same tree in NumPy, with the
     momentum from np.random.standard_normal, the direction of a doubling from np.random.randint(2) and then its merge uniform
     from np.random.random, and one np.random.random per leaf of a subtree after its first.  `totals` counts what the device's
-    proposal_state reports: n_leapfrog, n_divergent, n_max_depth, depth_sum."""
+    proposal_state reports: n_leapfrog, n_divergent, n_max_depth, depth_sum.  `adapt_mass` is HMC's: warm-up adaptation of the
+    inverse mass, pooled over all chains on the device and per chain on the host."""
 
-    def __init__(self, scaling=0.1, max_depth=8, inv_mass=None, adaptive=False, target_accept=0.8, gamma=1.01, period=100):
+    def __init__(self, scaling=0.1, max_depth=8, inv_mass=None, adaptive=False, target_accept=0.8, gamma=1.01, period=100, adapt_mass=0):
         if int(max_depth) != max_depth or not 1 <= max_depth <= 10:
             raise ValueError("max_depth must be an integer in 1 .. 10, not %r" % (max_depth,))
         if not 0.0 < target_accept < 1.0:
             raise ValueError("target_accept must lie in (0, 1), not %r" % (target_accept,))
-        super().__init__(scaling, 1, inv_mass, adaptive, gamma, period)
+        super().__init__(scaling, 1, inv_mass, adaptive, gamma, period, adapt_mass)
         self.n_leapfrog = None  # (chosen per step)
         self.max_depth, self.target_accept = int(max_depth), float(target_accept)
         self.alpha_star = self.target_accept
@@ -450,11 +537,14 @@ class NUTS(HMC):
                 self.scaling = np.exp(np.log(self.scaling) + self.gamma ** -self.k * (self._stat_sum / self.period - self.alpha_star))
                 self.k += 1
             self._stat_sum = 0.0
+        if self.adapt_mass:
+            self._adapt_mass(kwargs["parameters"])
 
     def _lowering(self):
-        return dict(kind=_lib.PROP_NUTS, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
-                    period=int(self.period), max_depth=self.max_depth, target_accept=self.target_accept,
-                    inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+        low = dict(kind=_lib.PROP_NUTS, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
+                   period=int(self.period), max_depth=self.max_depth, target_accept=self.target_accept,
+                   inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+        return dict(low, adapt_mass=self.adapt_mass) if self.adapt_mass else low
 
 
 class AdaptiveMetropolis(GaussianRandomWalk):
