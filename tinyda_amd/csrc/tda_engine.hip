@@ -374,6 +374,9 @@ struct tda_engine {
   int64_t mass_updates = 0;  // window ends applied
   DevBuf<double> mass_mean, mass_M2;  // [NP][DP]: the chains' running moments of the window
   DevBuf<unsigned int> mass_refused;  // [1]: entries that a window's end left unchanged
+  // a fixed dense inverse mass W = L L^T of HMC / NUTS (tda_engine_set_dense_mass, tda_host_dense_mass.inc): configuration as well
+  std::vector<double> dense_chol_h;  // [d][d], the lower-triangular factor L; empty: the diagonal mass above
+  DevBuf<double> dense_chol;         // [2][DP][DP]: L and behind it L^T, zero outside the triangle and in the padding (uploaded by tda_engine_init)
   DevBuf<double> q_mean_d, lq, qzblk, qzblk2[2];
   double am_sd = 1.0;
   bool L_shared = true;
@@ -1031,7 +1034,7 @@ int fill_user_mala_args(tda_engine* e, const Level& lv, UserMalaArgs& ga) {
 int fill_user_hmc_args(tda_engine* e, const Level& lv, UserHmcArgs& ha) {
   if (int rc = fill_user_mala_args(e, lv, ha)) return rc;
   ha.n_leapfrog = e->hmc_n_leapfrog;
-  ha.inv_mass = e->hmc_inv_mass.p;
+  ha.inv_mass = e->dense_chol_h.empty() ? e->hmc_inv_mass.p : e->dense_chol.p;  // (a dense program reads [2][DP][DP] there)
   return TDA_OK;
 }
 
@@ -1048,7 +1051,7 @@ int fill_user_nuts_args(tda_engine* e, const Level& lv, UserNutsArgs& na) {
   if (int rc = fill_user_mala_args(e, lv, na)) return rc;
   na.max_depth = e->nuts_max_depth;
   na.ck_off = (int)(user_mala_lds(lv.uprog_mala.spec, na.m) / sizeof(double));
-  na.inv_mass = e->hmc_inv_mass.p;
+  na.inv_mass = e->dense_chol_h.empty() ? e->hmc_inv_mass.p : e->dense_chol.p;  // (a dense program reads [2][DP][DP] there)
   na.seed = e->cfg.seed;
   na.chain_offset = e->cfg.chain_offset;
   na.accsum = e->nuts_accsum.p;
@@ -1169,6 +1172,7 @@ UserProgramSpec user_program_spec(const tda_engine* e, const Level& lv, bool mal
   s.gradient_wave = mala && lv.forms.gradient_wave;
   s.hmc = mala && e->pp.kind == TDA_PROP_HMC;
   s.nuts = mala && e->pp.kind == TDA_PROP_NUTS;
+  s.dense_mass = (s.hmc || s.nuts) && !e->dense_chol_h.empty();
   return s;
 }
 
@@ -1417,6 +1421,7 @@ int64_t tda_release_cached_memory(void) { return (int64_t)g_pool.trim(); }
 
 // ---- the rest of the ABI, by family (textual includes: one translation unit) ----
 #include "tda_host_mass.inc"
+#include "tda_host_dense_mass.inc"
 #include "tda_host_setup.inc"
 #include "tda_host_dreamz_archive.inc"
 #include "tda_host_state.inc"

@@ -278,10 +278,25 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     const size_t dyn = user_mala_lds(l0.uprog_mala.spec, l0.m), ck = user_nuts_checkpoint_lds(e->nuts_max_depth, DP);
     int stat = 0;
     HIP_TRY(hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, l0.uprog_mala.steps));
+    if ((size_t)stat + dyn + ck > USER_LDS_MAX && l0.uprog_mala.spec.dense_mass)
+      return fail(TDA_ERR_UNSUPPORTED, "NUTS over a source-defined model needs more than 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient, "
+                                       "TDA_WORKSPACE and %zu bytes for the operand of the dense mass's products) + %zu bytes for its %d outputs + %zu bytes for the "
+                                       "checkpoints of max_depth = %d over %d padded parameters = %zu bytes",
+                  stat, user_dense_mass_lds(), dyn, l0.m, ck, e->nuts_max_depth, DP, (size_t)stat + dyn + ck);
     if ((size_t)stat + dyn + ck > USER_LDS_MAX)
       return fail(TDA_ERR_UNSUPPORTED, "NUTS over a source-defined model holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient and "
                                        "TDA_WORKSPACE) + %zu bytes for its %d outputs + %zu bytes for the checkpoints of max_depth = %d over %d padded parameters",
                   stat, dyn, l0.m, ck, e->nuts_max_depth, DP);
+  }
+  if (user_mala && e->pp.kind == TDA_PROP_HMC && e->levels[0].uprog_mala.spec.dense_mass) {  // (HMC: the dense mass's 1 KiB may be what no longer fits)
+    const Level& l0 = e->levels[0];
+    const size_t dyn = user_mala_lds(l0.uprog_mala.spec, l0.m);
+    int stat = 0;
+    HIP_TRY(hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, l0.uprog_mala.steps));
+    if ((size_t)stat + dyn > USER_LDS_MAX)
+      return fail(TDA_ERR_UNSUPPORTED, "HMC over a source-defined model needs more than 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient, "
+                                       "TDA_WORKSPACE and %zu bytes for the operand of the dense mass's products) + %zu bytes for its %d outputs = %zu bytes",
+                  stat, user_dense_mass_lds(), dyn, l0.m, (size_t)stat + dyn);
   }
   if (!e->is_dreamz) {  // ---- Gaussian proposals: factor of the proposal covariance (DREAMZ has its archive instead) ----
   std::vector<double> L;
@@ -309,6 +324,17 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
       std::vector<double> wm(DP, 1.0);
       for (int j = 0; j < d && !e->hmc_inv_mass_h.empty(); ++j) wm[j] = e->hmc_inv_mass_h[j];
       if ((rc = e->hmc_inv_mass.upload(wm))) return rc;
+    }
+    if (leapfrog_proposal(e->pp.kind) && !e->dense_chol_h.empty()) {  // the dense factor and its transpose, zero outside the triangle and in the padding
+      std::vector<double> LL(2 * (size_t)DP * DP, 0.0);
+      for (int i = 0; i < d; ++i)
+        for (int j = 0; j <= i; ++j) {
+          LL[(size_t)i * DP + j] = e->dense_chol_h[(size_t)i * d + j];
+          LL[(size_t)DP * DP + (size_t)j * DP + i] = e->dense_chol_h[(size_t)i * d + j];
+        }
+      if ((rc = e->dense_chol.upload(LL))) return rc;
+    } else {
+      e->dense_chol.release();
     }
     e->mass_n = 0;
     e->mass_updates = 0;

@@ -73,6 +73,9 @@ int tda_engine_set_mass_adaptation(tda_engine* e, int64_t warmup_steps) {
   if (!e) return fail(TDA_ERR_INVALID, "null engine");
   if (!e->prop_set || e->is_dreamz || !leapfrog_proposal(e->pp.kind))
     return fail(TDA_ERR_STATE, "set_proposal with kind TDA_PROP_HMC or TDA_PROP_NUTS must precede set_mass_adaptation");
+  if (warmup_steps != 0 && !e->dense_chol_h.empty())
+    return fail(TDA_ERR_STATE, "set_mass_adaptation on an engine with a dense mass: the warm-up learns a diagonal mass, tda_engine_set_dense_mass "
+                               "fixed a dense one (switch it off with chol = NULL first)");
   const int64_t period = e->pp.period;
   if (warmup_steps < 0 || warmup_steps % period != 0 || (warmup_steps != 0 && warmup_steps < 2 * period))
     return fail(TDA_ERR_INVALID, "mass adaptation: warmup_steps = %lld must be a multiple of the period (%lld) and at least two periods (or 0: off)",
@@ -86,6 +89,8 @@ int tda_engine_get_mass(tda_engine* e, double* inv_mass, int64_t* info) {
   if (!e) return fail(TDA_ERR_INVALID, "null engine");
   if (!e->inited || e->is_dreamz || !leapfrog_proposal(e->pp.kind) || !e->hmc_inv_mass.p)
     return fail(TDA_ERR_STATE, "get_mass applies to an initialised HMC or NUTS engine");
+  if (!e->dense_chol_h.empty())
+    return fail(TDA_ERR_STATE, "get_mass reads a diagonal mass: this engine has a dense one, which tda_engine_get_dense_mass reads");
   HIP_TRY(hipSetDevice(e->cfg.device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (inv_mass)

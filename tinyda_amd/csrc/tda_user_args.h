@@ -101,7 +101,8 @@ struct UserMalaArgs {
 // configuration behind them.  `scaling` is the leapfrog step size.
 struct UserHmcArgs : UserMalaArgs {
   int n_leapfrog;          // leapfrog steps per proposal, >= 1
-  const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding
+  const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding.  A program built with -DTDA_DENSE_MASS:
+                           // [2][DP][DP], the factor L of the dense inverse mass and behind it L^T, zero outside the triangle and in the padding
 };
 
 // NUTS over a source-defined model (tda_user_nuts_steps; the algorithm: include/tinyda_amd_nuts.h): MALA's chain state, unit
@@ -112,7 +113,7 @@ struct UserHmcArgs : UserMalaArgs {
 struct UserNutsArgs : UserMalaArgs {
   int max_depth;           // doublings per tree at the most, 1 .. TDA_NUTS_MAX_DEPTH
   int ck_off;              // where the checkpoints start in the dynamic LDS, in doubles (behind the MALA program's s_sens)
-  const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding
+  const double* inv_mass;  // [DP]: the diagonal inverse mass, positive; ones in the padding ([2][DP][DP] under -DTDA_DENSE_MASS, as above)
   unsigned long long seed;
   long long step0, chain_offset;  // global step of this launch's step 0; global id of chain 0
   double* accsum;          // [NP]: the running period's sum of per-step acceptance statistics

@@ -71,9 +71,12 @@ struct UserProgramSpec {
                                 // gradient (the MALA program's requirements), without it over differences of the step program's objective
   bool hmc = false;             // (with mala) the HMC program: tda_user_hmc_steps in place of tda_user_mala_steps, everything else the MALA program's
   bool nuts = false;            // (with mala) the NUTS program: tda_user_nuts_steps in that place; the checkpoints of its trees are LDS behind the MALA program's
+  bool dense_mass = false;      // (with hmc or nuts) the dense inverse mass of include/tinyda_amd_dense_mass.h: the whitened momentum, two
+                                // matrix-vector products per leapfrog step, 1 KiB of static LDS more (s_vec)
   bool operator==(const UserProgramSpec& o) const {
     return mala == o.mala && loglike_source == o.loglike_source && prior_form == o.prior_form && forward_wave == o.forward_wave &&
-           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave && replay == o.replay && qoi_form == o.qoi_form && map == o.map && hmc == o.hmc && nuts == o.nuts;
+           gradient_wave == o.gradient_wave && loglike_wave == o.loglike_wave && replay == o.replay && qoi_form == o.qoi_form && map == o.map && hmc == o.hmc && nuts == o.nuts &&
+           dense_mass == o.dense_mass;
   }
 };
 
@@ -83,6 +86,8 @@ inline size_t user_mala_lds(const UserProgramSpec& spec, int m) { return (spec.l
 // dynamic LDS of tda_user_nuts_steps behind that: the U-turn checkpoints of a subtree, (momentum, running momentum sum) per row of
 // DP doubles, max_depth rows at the most
 inline size_t user_nuts_checkpoint_lds(int max_depth, int DP) { return 2 * (size_t)max_depth * (size_t)DP * sizeof(double); }
+// static LDS that a dense mass adds to tda_user_hmc_steps / tda_user_nuts_steps: s_vec[128], the operand of its two products
+constexpr size_t user_dense_mass_lds() { return 128 * sizeof(double); }
 // dynamic LDS of a program's kernels for m outputs: the MALA program's buffer, or the step program's s_out[m] under a wave form of
 // the model or of the likelihood (0 without one)
 inline size_t user_dynamic_lds(const UserProgramSpec& spec, int m) {
@@ -137,6 +142,7 @@ std::vector<const char*> user_program_options(const UserProgramSpec& s) {
   if (s.mala) opts.push_back("-DTDA_USER_MALA");
   if (s.mala && s.hmc) opts.push_back("-DTDA_USER_HMC");
   if (s.mala && s.nuts) opts.push_back("-DTDA_USER_NUTS");
+  if (s.mala && (s.hmc || s.nuts) && s.dense_mass) opts.push_back("-DTDA_DENSE_MASS");
   if (s.map) opts.push_back("-DTDA_USER_MAP");
   if (s.prior_form) opts.push_back("-DTDA_PRIOR_SOURCE");  // (with MALA: the source defines the prior's gradient too)
   if (s.prior_form == 2) opts.push_back("-DTDA_PRIOR_WAVE");

@@ -65,6 +65,10 @@
 // and one turns it into the NUTS program:
 //   -DTDA_USER_NUTS       (in addition to -DTDA_USER_MALA) the NUTS kernel (tda_user_nuts_steps) in that place: trees of leapfrog steps
 //                         that end at a U-turn, on the same log-posterior and gradient; tda_user_mala_grad0 stays as under HMC
+// and one gives either of the two a dense inverse mass:
+//   -DTDA_DENSE_MASS      (in addition to -DTDA_USER_HMC / -DTDA_USER_NUTS) the arithmetic of include/tinyda_amd_dense_mass.h: the kernel
+//                         holds the whitened momentum q = L^T p of the inverse mass W = L L^T, `inv_mass` points at [2][DP][DP], L and
+//                         behind it L^T, and the two products v = L q, r = L^T g go through tda_dense_product and s_vec
 #include <hip/hip_runtime.h>
 #include "tda_user_args.h"
 __device__ double tda_forward(const double* theta, int dim, int o);
@@ -616,6 +620,35 @@ __device__ __forceinline__ void tda_map_gradient(const UserMapArgs& a, const dou
 #endif
 }
 #else
+#ifdef TDA_DENSE_MASS
+// y_i = sum_j M[j][i] x_j for the parameters i = lane, lane + 64 (include/tinyda_amd_dense_mass.h, "The two products"): M is
+// [DP][DP] row-major, zero outside the triangle and in the padding, so M = L gives r = L^T g and M = L^T gives v = L q.  The sum
+// runs over j = 0, 1, .., d - 1 in that order from 0.0, one fused multiply-add per term: the terms outside the triangle add exact
+// zeros.  Lane i reads M[j][i]: consecutive lanes on consecutive addresses, one row of 8 DP bytes per j, the same row for every
+// chain on the device; the operand x_j is broadcast from s_vec.  A lane without a parameter gets 0 (whatever x holds: 0 * NaN
+// is not 0).  Barriers: the first puts the readers of s_vec of the product before behind it, the second the stores before the
+// reads; called from the converged wave only.
+__device__ __forceinline__ void tda_dense_product(const double* __restrict__ M, int d, int DP, double* s_vec, int lane, double x, double x2, double& y, double& y2) {
+  __syncthreads();
+  s_vec[lane] = x;
+  s_vec[lane + 64] = x2;
+  __syncthreads();
+  double acc = 0.0, acc2 = 0.0;
+  if (DP > 64) {  // (DP = 128: both slots of a lane lie inside a row)
+#pragma unroll 4
+    for (int j = 0; j < d; ++j) {
+      const double xj = s_vec[j];
+      acc = fma(M[(size_t)j * DP + lane], xj, acc);
+      acc2 = fma(M[(size_t)j * DP + lane + 64], xj, acc2);
+    }
+  } else if (lane < DP) {
+#pragma unroll 4
+    for (int j = 0; j < d; ++j) acc = fma(M[(size_t)j * DP + lane], s_vec[j], acc);
+  }
+  y = lane < d ? acc : 0.0;
+  y2 = lane + 64 < d ? acc2 : 0.0;
+}
+#endif
 #if defined(TDA_USER_NUTS)
 // The no-U-turn sampler in place of tda_user_mala_steps (the algorithm, step by step: include/tinyda_amd_nuts.h): multinomial NUTS
 // in iterative form, one wave per chain.  Both edges of the tree, its candidate, the new subtree's candidate, the moving leaf and
@@ -655,6 +688,9 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
 #ifdef TDA_GRADIENT_WAVE
   __shared__ double s_grad[128];
 #endif
+#ifdef TDA_DENSE_MASS
+  __shared__ double s_vec[128];  // the broadcast operand of tda_dense_product
+#endif
   const int lane = threadIdx.x, lane2 = lane + 64;
   const long long c = blockIdx.x;
   if (c >= a.N) return;
@@ -665,8 +701,14 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
   double gc = lj ? a.grad[row + lane] : 0.0, gc2 = lj2 ? a.grad[row + lane2] : 0.0;
   double lp = a.lp[c], ll = a.ll[c];
   const double eps = a.scaling[c];
+#ifdef TDA_DENSE_MASS
+  // p, pl, pr, rho, rs and the checkpoints below hold the whitened momentum q = L^T p and its sums
+  const double* const chol = a.inv_mass;
+  const double* const cholT = a.inv_mass + (size_t)a.DP * a.DP;
+#else
   const double w = lj ? a.inv_mass[lane] : 1.0, w2 = lj2 ? a.inv_mass[lane2] : 1.0;
   const double sw = sqrt(w), sw2 = sqrt(w2);
+#endif
   const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
   const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
   (void)pm, (void)pinv, (void)pm2, (void)pinv2;
@@ -677,8 +719,13 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
   for (int s = 0; s < a.S; ++s) {
     const double* z = a.inc + ((size_t)s * a.NP + c) * a.DP;
     const unsigned gstep = (unsigned)(a.step0 + s);
+#ifdef TDA_DENSE_MASS
+    const double p0 = lj ? z[lane] : 0.0, p02 = lj2 ? z[lane2] : 0.0;  // q = z: the momentum L^-T z ~ N(0, W^-1)
+    const double h0 = -(lp + ll) + 0.5 * tda_wave_sum(p0 * p0 + p02 * p02);
+#else
     const double p0 = lj ? z[lane] / sw : 0.0, p02 = lj2 ? z[lane2] / sw2 : 0.0;  // momentum ~ N(0, 1 / w)
     const double h0 = -(lp + ll) + 0.5 * tda_wave_sum(w * (p0 * p0) + w2 * (p02 * p02));
+#endif
     // the tree: its edges (l: backward, r: forward), the sum of its momenta, its log-weight, its candidate
     double lth = cur, lth2 = cur2, pl = p0, pl2 = p02, lg = gc, lg2 = gc2;
     double rth = cur, rth2 = cur2, pr = p0, pr2 = p02, rg = gc, rg2 = gc2;
@@ -696,11 +743,24 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
       // the new subtree: its candidate, its log-weight, the sum of its momenta
       double sth = 0.0, sth2 = 0.0, sg = 0.0, sg2 = 0.0, slp = 0.0, sll = 0.0, LWs = 0.0, rs = 0.0, rs2 = 0.0;
       const int nl = 1 << j;
+#ifdef TDA_DENSE_MASS
+      double r, r2;  // r = L^T g at the moving leaf: of the edge here, of each new leaf below
+      tda_dense_product(chol, a.d, a.DP, s_vec, lane, g, g2, r, r2);
+#endif
       for (int n = 0; n < nl; ++n) {
+#ifdef TDA_DENSE_MASS
+        p += he * r;
+        p2 += he * r2;
+        double v, v2;
+        tda_dense_product(cholT, a.d, a.DP, s_vec, lane, p, p2, v, v2);  // v = L q
+        th += e * v;  // (a lane without a parameter keeps q = v = r = 0 and th = 0)
+        th2 += e * v2;
+#else
         p += he * g;
         p2 += he * g2;
         th += e * (w * p);  // (a lane without a parameter keeps p = 0 and th = 0)
         th2 += e * (w2 * p2);
+#endif
         __syncthreads();
         s_th[lane] = th;
         s_th[lane2] = th2;
@@ -746,10 +806,17 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
         g = lj ? TDA_PRIOR_GRAD(th, pm, pinv, lane) + tda_gradient(s_th, a.d, s_sens, a.m, lane) : 0.0;
         g2 = lj2 ? TDA_PRIOR_GRAD(th2, pm2, pinv2, lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
 #endif
+#ifdef TDA_DENSE_MASS
+        tda_dense_product(chol, a.d, a.DP, s_vec, lane, g, g2, r, r2);
+        p += he * r;
+        p2 += he * r2;
+        const double h = -post_n + 0.5 * tda_wave_sum(p * p + p2 * p2);
+#else
         p += he * g;
         p2 += he * g2;
         // (a gradient that is not finite leaves a NaN momentum: the energy is NaN and the leaf divergent)
         const double h = -post_n + 0.5 * tda_wave_sum(w * (p * p) + w2 * (p2 * p2));
+#endif
         if (__builtin_amdgcn_readfirstlane((h != h || h - h0 > 1000.0) ? 1 : 0)) {
           stop = 1;
           break;
@@ -785,7 +852,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
             const double* const ck = s_ck + (size_t)k * 2 * a.DP;
             const double pa = lj ? ck[lane] : 0.0, pa2 = lj2 ? ck[lane2] : 0.0;
             const double rr = lj ? (rs - ck[a.DP + lane]) + pa : 0.0, rr2 = lj2 ? (rs2 - ck[a.DP + lane2]) + pa2 : 0.0;
+#ifdef TDA_DENSE_MASS
+            const double da = tda_wave_sum(pa * rr + pa2 * rr2), db = tda_wave_sum(p * rr + p2 * rr2);  // p_a^T W rho_p = q_a . rho_q
+#else
             const double da = tda_wave_sum((w * pa) * rr + (w2 * pa2) * rr2), db = tda_wave_sum((w * p) * rr + (w2 * p2) * rr2);
+#endif
             turn |= (da > 0.0 && db > 0.0) ? 0 : 1;
           }
           if (__builtin_amdgcn_readfirstlane(turn)) {
@@ -809,7 +880,11 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_nuts_steps(const UserN
         lth = th, lth2 = th2, pl = p, pl2 = p2, lg = g, lg2 = g2;
       }
       depth = j + 1;
+#ifdef TDA_DENSE_MASS
+      const double da = tda_wave_sum(pl * rho + pl2 * rho2), db = tda_wave_sum(pr * rho + pr2 * rho2);
+#else
       const double da = tda_wave_sum((w * pl) * rho + (w2 * pl2) * rho2), db = tda_wave_sum((w * pr) * rho + (w2 * pr2) * rho2);
+#endif
       if (__builtin_amdgcn_readfirstlane((da > 0.0 && db > 0.0) ? 0 : 1)) {
         stop = 3;
         break;
@@ -876,6 +951,9 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_hmc_steps(const UserHm
 #ifdef TDA_GRADIENT_WAVE
   __shared__ double s_grad[128];  // J^T sens at the moving position, all parameters from one tda_gradient_wave call
 #endif
+#ifdef TDA_DENSE_MASS
+  __shared__ double s_vec[128];  // the broadcast operand of tda_dense_product
+#endif
   const int lane = threadIdx.x, lane2 = lane + 64;
   const long long c = blockIdx.x;
   if (c >= a.N) return;
@@ -885,23 +963,44 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_hmc_steps(const UserHm
   double gc = lj ? a.grad[row + lane] : 0.0, gc2 = lj2 ? a.grad[row + lane2] : 0.0;  // gradient at the current state
   double lp = a.lp[c], ll = a.ll[c];
   const double eps = a.scaling[c], he = 0.5 * eps;
+#ifdef TDA_DENSE_MASS
+  // p below holds the whitened momentum q = L^T p of include/tinyda_amd_dense_mass.h
+  const double* const chol = a.inv_mass;
+  const double* const cholT = a.inv_mass + (size_t)a.DP * a.DP;
+#else
   const double w = lj ? a.inv_mass[lane] : 1.0, w2 = lj2 ? a.inv_mass[lane2] : 1.0;
   const double sw = sqrt(w), sw2 = sqrt(w2);
+#endif
   const double pm = lj ? a.pr_mean[lane] : 0.0, pinv = lj ? a.pr_pinv[lane] : 0.0;
   const double pm2 = lj2 ? a.pr_mean[lane2] : 0.0, pinv2 = lj2 ? a.pr_pinv[lane2] : 0.0;
   (void)pm, (void)pinv, (void)pm2, (void)pinv2;
   int nacc = 0;
   for (int s = 0; s < a.S; ++s) {
     const double* z = a.inc + ((size_t)s * a.NP + c) * a.DP;
+#ifdef TDA_DENSE_MASS
+    double p = lj ? z[lane] : 0.0, p2 = lj2 ? z[lane2] : 0.0;  // q = z: the momentum L^-T z ~ N(0, W^-1)
+    const double k0 = 0.5 * tda_wave_sum(p * p + p2 * p2);
+    double fr, fr2, v, v2;  // fr: the r = L^T g of include/tinyda_amd_dense_mass.h
+    tda_dense_product(chol, a.d, a.DP, s_vec, lane, gc, gc2, fr, fr2);
+    p += he * fr;
+    p2 += he * fr2;
+#else
     double p = lj ? z[lane] / sw : 0.0, p2 = lj2 ? z[lane2] / sw2 : 0.0;  // momentum ~ N(0, 1 / w)
     const double k0 = 0.5 * tda_wave_sum(w * (p * p) + w2 * (p2 * p2));
     p += he * gc;
     p2 += he * gc2;
+#endif
     double th = cur, th2 = cur2, g = gc, g2 = gc2, lp_n = lp, ll_n = ll, post_n = lp + ll;
     int alive = 1;
     for (int i = 1; i <= a.n_leapfrog; ++i) {
+#ifdef TDA_DENSE_MASS
+      tda_dense_product(cholT, a.d, a.DP, s_vec, lane, p, p2, v, v2);  // v = L q
+      th += eps * v;  // (a lane without a parameter keeps q = v = r = 0 and th = 0)
+      th2 += eps * v2;
+#else
       th += eps * (w * p);  // (a lane without a parameter keeps p = 0 and th = 0)
       th2 += eps * (w2 * p2);
+#endif
       __syncthreads();
       s_th[lane] = th;
       s_th[lane2] = th2;
@@ -944,12 +1043,22 @@ extern "C" __global__ void __launch_bounds__(64) tda_user_hmc_steps(const UserHm
       g2 = lj2 ? TDA_PRIOR_GRAD(th2, pm2, pinv2, lane2) + tda_gradient(s_th, a.d, s_sens, a.m, lane2) : 0.0;
 #endif
       const double cc = i < a.n_leapfrog ? eps : he;
+#ifdef TDA_DENSE_MASS
+      tda_dense_product(chol, a.d, a.DP, s_vec, lane, g, g2, fr, fr2);
+      p += cc * fr;
+      p2 += cc * fr2;
+#else
       p += cc * g;
       p2 += cc * g2;
+#endif
     }
     // a gradient that is not finite leaves a NaN momentum: the next position's log-posterior is NaN and ends the trajectory, or
     // (at the last step) k1 is NaN, alpha is NaN and `u < NaN` is false
+#ifdef TDA_DENSE_MASS
+    const double k1 = 0.5 * tda_wave_sum(p * p + p2 * p2);
+#else
     const double k1 = 0.5 * tda_wave_sum(w * (p * p) + w2 * (p2 * p2));
+#endif
     double alpha = exp((post_n - (lp + ll)) + (k0 - k1));
     if (!alive || post_n != post_n) alpha = 0.0;
     const bool acc = a.u[(size_t)s * a.NP + c] < alpha;

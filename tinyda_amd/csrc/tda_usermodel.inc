@@ -123,6 +123,10 @@ int compile_user_program(const char* source, const UserProgramSpec& spec, int m,
           return fail(TDA_ERR_UNSUPPORTED, "a likelihood that couples outputs holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters, "
                                            "gradient and TDA_WORKSPACE) + %zu bytes for its %d outputs%s",
                       stat, dyn, m, mala ? " and their sensitivities" : "");
+        if (spec.dense_mass)  // (s_vec is part of `stat`, and may be what no longer fits)
+          return fail(TDA_ERR_UNSUPPORTED, "a wave-form model under a dense mass needs more than 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient, "
+                                           "TDA_WORKSPACE and %zu bytes for the operand of the dense mass's products) + %zu bytes for its %d outputs",
+                      stat, user_dense_mass_lds(), dyn, m);
         return fail(TDA_ERR_UNSUPPORTED, "a wave-form model holds at most 64 KiB of LDS per chain: this source needs %d bytes (parameters, gradient and "
                                          "TDA_WORKSPACE) + %zu bytes for its %d outputs",
                     stat, dyn, m);

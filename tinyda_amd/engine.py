@@ -110,7 +110,7 @@ class Engine:
 
     def set_proposal(self, kind, C_=None, scaling=1.0, adaptive=False, gamma=1.01, period=100, sd=None,
                      epsilon=1e-6, t0=0, block_moments=False, q_mean=None, state_operator=None, noise_operator=None, spectrum=None,
-                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8, adapt_mass=0):
+                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8, adapt_mass=0, dense_mass=None):
         Cm = None if C_ is None else _f64(C_)
         p = _lib.tda_proposal_params(C.sizeof(_lib.tda_proposal_params), kind, scaling, int(adaptive), period, gamma,
                                      _ptr(Cm), -1.0 if sd is None else sd, epsilon, t0, int(block_moments),
@@ -128,8 +128,30 @@ class Engine:
             self.set_hmc(n_leapfrog, inv_mass)
         if max_depth is not None:  # NUTS (kind 8)
             self.set_nuts(max_depth, target_accept, inv_mass)
+        if dense_mass is not None:  # HMC / NUTS: the Cholesky factor of a fixed dense inverse mass
+            self.set_dense_mass(dense_mass)
         if adapt_mass:  # HMC / NUTS: warm-up adaptation of the mass
             self.set_mass_adaptation(adapt_mass)
+
+    def set_dense_mass(self, chol):
+        """a fixed dense inverse mass W = L L^T of HMC / NUTS (include/tinyda_amd_dense_mass.h), given by its lower-triangular factor
+        `chol` = L [dim, dim] (finite, positive diagonal, exact zeros above it); None switches it off.  After set_proposal(7 / 8,
+        ...) with its n_leapfrog / max_depth, before init; it replaces the diagonal inv_mass"""
+        L = None if chol is None else _f64(chol)
+        if L is not None and L.shape != (self.dim, self.dim):
+            raise ValueError("the factor of a dense mass is [dim, dim] = [%d, %d], not %r" % (self.dim, self.dim, L.shape))
+        self._ck(self.lib.tda_engine_set_dense_mass(self.h, _ptr(L)))
+
+    def get_dense_mass(self, out=None):
+        """the factor L [dim, dim] in force of an initialised HMC / NUTS engine with a dense mass, the bits the kernels multiply by.
+        out: a device tensor of that shape to copy into instead"""
+        if out is not None:
+            assert tuple(out.shape) == (self.dim, self.dim) and out.is_contiguous() and out.element_size() == 8
+            self._ck(self.lib.tda_engine_get_dense_mass(self.h, out.data_ptr()))
+            return out
+        L = np.empty((self.dim, self.dim))
+        self._ck(self.lib.tda_engine_get_dense_mass(self.h, _ptr(L)))
+        return L
 
     def set_mass_adaptation(self, warmup_steps):
         """adapt the diagonal inverse mass of HMC / NUTS during the first `warmup_steps` steps, pooled over the engine's chains

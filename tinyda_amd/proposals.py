@@ -311,6 +311,48 @@ def _mass_pool(mean, M2, n, inv_mass):
     return np.where(ok, w, inv_mass), int(np.sum(~ok))
 
 
+def dense_inv_mass(W):
+    """A dense inverse mass of HMC / NUTS (include/tinyda_amd_dense_mass.h), validated: -> (W [d, d], its lower Cholesky factor L,
+    W = L L^T).  W must be square, finite, exactly symmetric and positive definite (np.linalg.cholesky decides)."""
+    W = np.array(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != W.shape[1] or W.shape[0] < 1:
+        raise ValueError("inv_mass takes one finite, positive value per parameter, [d], or a symmetric positive definite matrix, [d, d]; not the shape %r" % (W.shape,))
+    if not np.all(np.isfinite(W)):
+        raise ValueError("a dense inv_mass must be finite")
+    if not np.array_equal(W, W.T):
+        raise ValueError("a dense inv_mass must be symmetric, W == W.T exactly: symmetrise it first, W = (W + W.T) / 2")
+    try:
+        L = np.linalg.cholesky(W)
+    except np.linalg.LinAlgError as exc:
+        raise ValueError("a dense inv_mass must be positive definite: np.linalg.cholesky failed (%s)" % (exc,)) from None
+    if not (np.all(np.isfinite(L)) and np.all(np.diag(L) > 0.0)):
+        raise ValueError("a dense inv_mass must be positive definite: its Cholesky factor is not finite with a positive diagonal")
+    return W, np.tril(L)
+
+
+class _Metric:
+    """The arithmetic that the mass enters, for the host classes below: a diagonal inverse mass w on the momentum p, or a dense one
+    W = L L^T on the whitened momentum q = L^T p (include/tinyda_amd_dense_mass.h); `p` below is p or q accordingly."""
+
+    def __init__(self, w, L):
+        self.w, self.L = w, L
+
+    def draw(self, z):  # the momentum of the step's unit normals
+        return z / np.sqrt(self.w) if self.L is None else z
+
+    def kinetic(self, p):
+        return 0.5 * np.sum(self.w * (p * p)) if self.L is None else 0.5 * np.sum(p * p)
+
+    def force(self, g):  # what a half step adds to the momentum, per unit of step size
+        return g if self.L is None else self.L.T @ g
+
+    def velocity(self, p):
+        return self.w * p if self.L is None else self.L @ p
+
+    def dot(self, pa, rho):  # p_a^T W rho
+        return np.sum((self.w * pa) * rho) if self.L is None else np.sum(pa * rho)
+
+
 class HMC(MALA):
     """Hamiltonian Monte Carlo (an extension: the reference has none): per proposal a momentum p = z / sqrt(w) from d unit normals
     z, `n_leapfrog` leapfrog steps of size `scaling` under the diagonal inverse mass w = `inv_mass` (None: 1) on the log-posterior
@@ -326,14 +368,25 @@ class HMC(MALA):
     diminishing gain restarts at every update of the mass.  On the device path the variances are pooled over all chains of the
     engine, which share one mass vector.  On the host path every chain has its own copy of the proposal and adapts from its own
     window alone, on the same schedule, with the same regulariser and the same restart: pooling over chains exists only on the
-    device.  `mass_updates` and `mass_refused` count the window ends applied and the entries they left unchanged."""
+    device.  `mass_updates` and `mass_refused` count the window ends applied and the entries they left unchanged.
+
+    A two-dimensional `inv_mass` = W [d, d] is a fixed dense inverse mass (symmetric positive definite; `W == W.T` exactly), as
+    include/tinyda_amd_dense_mass.h writes it out: its Cholesky factor is computed once and kept as `chol_inv_mass`, the momentum
+    is held whitened, q = L^T p, and a leapfrog step is q += (e/2) L^T g; theta += e L q; q += (e/2) L^T g'.  It lowers wherever
+    the diagonal mass lowers.  `adapt_mass` learns a diagonal and is refused beside it; `mass_from_samples` turns a pilot run
+    into such a matrix."""
 
     alpha_star = 0.65
 
     def __init__(self, scaling=0.1, n_leapfrog=8, inv_mass=None, adaptive=False, gamma=1.01, period=100, adapt_mass=0):
         if int(n_leapfrog) != n_leapfrog or not 1 <= n_leapfrog <= 1024:
             raise ValueError("n_leapfrog must be an integer in 1 .. 1024, not %r" % (n_leapfrog,))
-        if inv_mass is not None:
+        self.chol_inv_mass = None
+        if inv_mass is not None and np.ndim(inv_mass) >= 2:
+            inv_mass, self.chol_inv_mass = dense_inv_mass(inv_mass)
+            if adapt_mass:
+                raise ValueError("adapt_mass = %r with a dense inv_mass: the warm-up adaptation learns a diagonal mass" % (adapt_mass,))
+        elif inv_mass is not None:
             inv_mass = np.atleast_1d(np.asarray(inv_mass, dtype=np.float64)).copy()
             if inv_mass.ndim != 1 or not np.all(np.isfinite(inv_mass) & (inv_mass > 0)):
                 raise ValueError("inv_mass takes one finite, positive value per parameter")
@@ -348,7 +401,7 @@ class HMC(MALA):
 
     def setup_proposal(self, **kwargs):
         super().setup_proposal(**kwargs)
-        if self.inv_mass is not None and self.inv_mass.shape != (self.d,):
+        if self.inv_mass is not None and self.inv_mass.shape != ((self.d,) if self.chol_inv_mass is None else (self.d, self.d)):
             raise ValueError("inv_mass has %d entries for %d parameters" % (self.inv_mass.shape[0], self.d))
         if self.adapt_mass and self.inv_mass is None:
             self.inv_mass = np.ones(self.d)
@@ -380,23 +433,26 @@ class HMC(MALA):
         if self.adapt_mass:
             self._adapt_mass(kwargs["parameters"])
 
+    def _metric(self):
+        return _Metric(np.ones(self.d) if self.inv_mass is None else self.inv_mass, self.chol_inv_mass)
+
     def make_proposal(self, link):
         if not hasattr(link, "gradient"):
             link.gradient = self.compute_gradient(link)
-        eps, w = self.scaling, np.ones(self.d) if self.inv_mass is None else self.inv_mass
-        p = np.random.standard_normal(self.d) / np.sqrt(w)
-        k0 = 0.5 * np.sum(w * (p * p))
-        p = p + (0.5 * eps) * link.gradient
+        eps, M = self.scaling, self._metric()
+        p = M.draw(np.random.standard_normal(self.d))
+        k0 = M.kinetic(p)
+        p = p + (0.5 * eps) * M.force(link.gradient)
         theta = np.asarray(link.parameters, dtype=np.float64)
         self._end = None  # (the end point, its gradient, K0 - K1): None when the trajectory ended early
         for i in range(1, self.n_leapfrog + 1):
-            theta = theta + eps * (w * p)
+            theta = theta + eps * M.velocity(p)
             at = self.posterior.create_link(theta)
             if not np.isfinite(at.posterior):
                 return theta
             grad = self.compute_gradient(at)
-            p = p + (eps if i < self.n_leapfrog else 0.5 * eps) * grad
-        self._end = (theta, grad, k0 - 0.5 * np.sum(w * (p * p)))
+            p = p + (eps if i < self.n_leapfrog else 0.5 * eps) * M.force(grad)
+        self._end = (theta, grad, k0 - M.kinetic(p))
         return theta
 
     def get_acceptance(self, proposal_link, previous_link):
@@ -411,10 +467,16 @@ class HMC(MALA):
     def get_q(self, x_link, y_link):  # (the momentum is not part of a link: the energy difference is inside get_acceptance)
         return 0.0
 
-    def _lowering(self):
-        low = dict(kind=_lib.PROP_HMC, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
-                   period=int(self.period), n_leapfrog=self.n_leapfrog, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
+    def _lowered_mass(self, low):
+        """the mass in a plan: `inv_mass` [d] or None, and under a dense mass `dense_mass`, its factor [d, d] (the key is there only then)"""
+        if self.chol_inv_mass is not None:
+            return dict(low, inv_mass=None, dense_mass=self.chol_inv_mass.copy())
+        low = dict(low, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
         return dict(low, adapt_mass=self.adapt_mass) if self.adapt_mass else low  # (off: the plan is what it was)
+
+    def _lowering(self):
+        return self._lowered_mass(dict(kind=_lib.PROP_HMC, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
+                                       period=int(self.period), n_leapfrog=self.n_leapfrog))
 
 
 def _logaddexp(a, b):
@@ -434,7 +496,9 @@ class NUTS(HMC):
     momentum from np.random.standard_normal, the direction of a doubling from np.random.randint(2) and then its merge uniform
     from np.random.random, and one np.random.random per leaf of a subtree after its first.  `totals` counts what the device's
     proposal_state reports: n_leapfrog, n_divergent, n_max_depth, depth_sum.  `adapt_mass` is HMC's: warm-up adaptation of the
-    inverse mass, pooled over all chains on the device and per chain on the host."""
+    inverse mass, pooled over all chains on the device and per chain on the host.  A two-dimensional `inv_mass` is HMC's fixed
+    dense inverse mass (include/tinyda_amd_dense_mass.h): the edges, the momentum sums and the checkpoints then hold the whitened
+    momentum q = L^T p, and the U-turn test is a plain dot product of q's."""
 
     def __init__(self, scaling=0.1, max_depth=8, inv_mass=None, adaptive=False, target_accept=0.8, gamma=1.01, period=100, adapt_mass=0):
         if int(max_depth) != max_depth or not 1 <= max_depth <= 10:
@@ -451,10 +515,10 @@ class NUTS(HMC):
     def make_proposal(self, link):
         if not hasattr(link, "gradient"):
             link.gradient = self.compute_gradient(link)
-        eps, w = self.scaling, np.ones(self.d) if self.inv_mass is None else self.inv_mass
+        eps, M = self.scaling, self._metric()
         theta0 = np.asarray(link.parameters, dtype=np.float64)
-        p0 = np.random.standard_normal(self.d) / np.sqrt(w)
-        h0 = -link.posterior + 0.5 * np.sum(w * (p0 * p0))
+        p0 = M.draw(np.random.standard_normal(self.d))
+        h0 = -link.posterior + M.kinetic(p0)
         left = right = (theta0, p0, np.asarray(link.gradient, dtype=np.float64))
         rho, LW = p0, 0.0
         cand = (theta0, left[2], 0)  # (position, gradient, the number of the leaf in this step; 0: the initial state)
@@ -466,16 +530,16 @@ class NUTS(HMC):
                 theta, p, g = right if fwd else left
                 ck, sub, LWs, rs = {}, None, 0.0, None
                 for n in range(1 << j):
-                    p = p + (0.5 * e) * g
-                    theta = theta + e * (w * p)
+                    p = p + (0.5 * e) * M.force(g)
+                    theta = theta + e * M.velocity(p)
                     at = self.posterior.create_link(theta)
                     nleaf += 1
                     if not np.isfinite(at.posterior):
                         stop = "divergent"
                         break
                     g = np.asarray(self.compute_gradient(at), dtype=np.float64)
-                    p = p + (0.5 * e) * g
-                    h = -at.posterior + 0.5 * np.sum(w * (p * p))
+                    p = p + (0.5 * e) * M.force(g)
+                    h = -at.posterior + M.kinetic(p)
                     if np.isnan(h) or h - h0 > 1000.0:
                         stop = "divergent"
                         break
@@ -495,7 +559,7 @@ class NUTS(HMC):
                         for k in range(top, top - ones, -1):
                             pa, ra = ck[k]
                             rr = (rs - ra) + pa
-                            if not (np.sum((w * pa) * rr) > 0.0 and np.sum((w * p) * rr) > 0.0):
+                            if not (M.dot(pa, rr) > 0.0 and M.dot(p, rr) > 0.0):
                                 turn = True
                         if turn:
                             stop = "uturn_subtree"
@@ -510,7 +574,7 @@ class NUTS(HMC):
                 else:
                     left = (theta, p, g)
                 depth = j + 1
-                if not (np.sum((w * left[1]) * rho) > 0.0 and np.sum((w * right[1]) * rho) > 0.0):
+                if not (M.dot(left[1], rho) > 0.0 and M.dot(right[1], rho) > 0.0):
                     stop = "uturn_tree"
                     break
         self._stat = asum / nleaf
@@ -541,10 +605,8 @@ class NUTS(HMC):
             self._adapt_mass(kwargs["parameters"])
 
     def _lowering(self):
-        low = dict(kind=_lib.PROP_NUTS, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
-                   period=int(self.period), max_depth=self.max_depth, target_accept=self.target_accept,
-                   inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
-        return dict(low, adapt_mass=self.adapt_mass) if self.adapt_mass else low
+        return self._lowered_mass(dict(kind=_lib.PROP_NUTS, C_=None, scaling=float(self.scaling), adaptive=bool(self.adaptive), gamma=float(self.gamma),
+                                       period=int(self.period), max_depth=self.max_depth, target_accept=self.target_accept))
 
 
 class AdaptiveMetropolis(GaussianRandomWalk):

@@ -295,3 +295,43 @@ def ess_summary(samples, burnin=0):
     arr = np.asarray(samples)[burnin:]
     vals = np.array([ess_bulk(arr[:, :, j].T) for j in range(arr.shape[2])])
     return dict(ess_min=float(np.nanmin(vals)), ess_median=float(np.nanmedian(vals)), ess=vals)
+
+
+def mass_from_samples(result, burnin=0, dense=True, chunk_rows=256):
+    """The pilot-run workflow in one line: the inverse mass for tinyda_amd.HMC / NUTS(inv_mass=...) from the recorded parameters
+    of a result of sample(), all chains pooled, rows [burnin:].  dense=True: the regularised pooled covariance [d, d] (a dense
+    mass, include/tinyda_amd_dense_mass.h); dense=False: the regularised pooled variances [d].  With T the number of pooled
+    states the regulariser is Stan's, the formula of include/tinyda_amd_mass.h:
+        cov * T / (T + 5) + 1e-3 * 5 / (T + 5) * I       (on the variances alone for a diagonal mass)
+    with cov the sample covariance about the pooled mean (divisor T - 1, as np.cov).  Computed with torch in float64 in chunks of
+    `chunk_rows` whole rows, where the records are: those of a device run stay in HBM, and only the [d, d] result crosses to the
+    host.  Returns a NumPy array; the dense one is exactly symmetric."""
+    import torch
+
+    chains = [result["chain_%d" % i] for i in range(result["n_chains"])] if result.get("sampler") == "MH" else None
+    recs = chains[0]._records if chains and isinstance(chains[0], DeviceChain) else None
+    if recs is not None and recs.n_chains == len(chains) and all(
+            isinstance(c, DeviceChain) and c._records is recs and c._chain == i and c._rows == slice(None) for i, c in enumerate(chains)):
+        P = recs.parameters[burnin:]  # [R, N, d], wherever the run left it
+        P = P if hasattr(P, "data_ptr") else torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64))
+    else:  # host records (lists of links), hierarchies: the finest chains, gathered on the host
+        got = get_samples(result, "parameters", burnin=burnin)
+        P = torch.from_numpy(np.ascontiguousarray(np.stack([got["chain_%d" % i] for i in range(got["n_chains"])], axis=1), dtype=np.float64))
+    R, N, d = (int(n) for n in P.shape)
+    T = R * N
+    if T < 2:
+        raise ValueError("mass_from_samples needs at least two recorded states after burnin = %d, not %d" % (burnin, T))
+    P = P.to(torch.float64)
+    mean = torch.zeros(d, dtype=torch.float64, device=P.device)
+    for r in range(0, R, chunk_rows):
+        mean += P[r:r + chunk_rows].reshape(-1, d).sum(dim=0)
+    mean /= float(T)
+    S = torch.zeros((d, d) if dense else (d,), dtype=torch.float64, device=P.device)
+    for r in range(0, R, chunk_rows):
+        X = P[r:r + chunk_rows].reshape(-1, d) - mean
+        S += X.T @ X if dense else (X * X).sum(dim=0)
+    cov = (S / float(T - 1)).cpu().numpy()
+    if not dense:
+        return cov * T / (T + 5.0) + 1e-3 * 5.0 / (T + 5.0)
+    cov = 0.5 * (cov + cov.T)
+    return cov * T / (T + 5.0) + 1e-3 * 5.0 / (T + 5.0) * np.eye(d)
