@@ -226,6 +226,13 @@ DENSE_MASS_SYMBOLS = {
     "tda_engine_get_dense_mass": (C.c_int, [_P, _P]),
 }
 
+# every symbol include/tinyda_amd_dense_mass_adaptation.h declares: bound by load() only, as the tables above
+DENSE_MASS_ADAPT_SYMBOLS = {
+    "tda_engine_set_dense_mass_adaptation": (C.c_int, [_P, C.c_int64]),
+    "tda_engine_get_dense_mass_adaptation": (C.c_int, [_P, _P]),
+    "tda_dense_mass_window": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -267,7 +274,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # missing ROCm runtime etc.
         raise EngineError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()) + list(NUTS_SYMBOLS.items()) + list(MASS_SYMBOLS.items()) + list(DENSE_MASS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(REPLAY_SYMBOLS.items()) + list(OPTIMIZE_SYMBOLS.items()) + list(HMC_SYMBOLS.items()) + list(NUTS_SYMBOLS.items()) + list(MASS_SYMBOLS.items()) + list(DENSE_MASS_SYMBOLS.items()) + list(DENSE_MASS_ADAPT_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -361,16 +361,20 @@ class LazyProposalState(Mapping):
     times as long as the 2000 iterations that produced them, and hardly any caller looks at them.
     After an HMC / NUTS run with adapt_mass > 0 (`with_mass`) it also holds `inv_mass` ([dim], the mass in force: copied out of the
     engine into device memory before it closes, read when the state is first indexed), `mass_updates` (window ends applied) and
-    `mass_refused` (entries that a window end left unchanged)."""
+    `mass_refused` (entries that a window end left unchanged).  With adapt_dense=True `inv_mass` is [dim, dim], L L^T of the factor in
+    force formed with torch where the factor lives, `chol_inv_mass` (that factor L) follows it, and `mass_refused` counts the window
+    ends that left the whole factor unchanged."""
 
     _MASS_KEYS = ("inv_mass", "mass_updates", "mass_refused")
+    _DENSE_MASS_KEYS = ("inv_mass", "chol_inv_mass", "mass_updates", "mass_refused")
 
     def __init__(self, snapshot, n_chains, dim, want_am):
         self._snap, self._shape, self._want_am, self._data = snapshot, (n_chains, dim), want_am, None
-        self._mass, self._has_mass = None, False
+        self._mass, self._has_mass, self._dense_mass = None, False, False
 
-    def with_mass(self, inv_mass, info):
-        self._mass, self._has_mass = (inv_mass, info), True
+    def with_mass(self, inv_mass, info, dense=False):
+        """inv_mass: the diagonal mass [dim], or with dense=True the factor L [dim, dim], as a device tensor"""
+        self._mass, self._has_mass, self._dense_mass = (inv_mass, info), True, bool(dense)
         return self
 
     def _load(self):
@@ -380,7 +384,11 @@ class LazyProposalState(Mapping):
             self._snap = None
             if self._mass is not None:
                 w, info = self._mass
-                self._data = dict(self._data, inv_mass=w.cpu().numpy(), mass_updates=info["updates"], mass_refused=info["refused"])
+                if self._dense_mass:
+                    self._data = dict(self._data, inv_mass=(w @ w.T).cpu().numpy(), chol_inv_mass=w.cpu().numpy(), mass_updates=info["updates"],
+                                      mass_refused=info["refused"])
+                else:
+                    self._data = dict(self._data, inv_mass=w.cpu().numpy(), mass_updates=info["updates"], mass_refused=info["refused"])
                 self._mass = None
         return self._data
 
@@ -388,10 +396,13 @@ class LazyProposalState(Mapping):
         return self._load()[key]
 
     def __iter__(self):
-        return iter(("scaling", "C", "am_mu", "am_sigma", "t", "k") + (self._MASS_KEYS if self._has_mass else ()))
+        return iter(("scaling", "C", "am_mu", "am_sigma", "t", "k") + self._mass_keys())
+
+    def _mass_keys(self):
+        return (self._DENSE_MASS_KEYS if self._dense_mass else self._MASS_KEYS) if self._has_mass else ()
 
     def __len__(self):
-        return 6 + (3 if self._has_mass else 0)
+        return 6 + len(self._mass_keys())
 
     # pickle / copy: the snapshot is a ctypes handle (not picklable, and a shallow copy would free it twice) -- a copy of any
     # kind is the materialised state, a plain dict of arrays, as the reference's result dict is plain Python
@@ -437,7 +448,7 @@ def _materialised_proposal_state(data, shape, want_am):
         st = NutsProposalState(None, shape[0], shape[1], None, 0)
     else:
         st = LazyProposalState(None, shape[0], shape[1], want_am)
-    st._data, st._has_mass = data, "inv_mass" in data
+    st._data, st._has_mass, st._dense_mass = data, "inv_mass" in data, "chol_inv_mass" in data
     return st
 
 
@@ -503,10 +514,13 @@ def _configure_engine(eng, plan, prior, initial_parameters, chain_offset, seed, 
 
 
 def _mass_of(eng, prop, torch, tdev):
-    """(the inverse mass as a device tensor, the adaptation's counters) of a run with adapt_mass > 0; None otherwise"""
+    """(the inverse mass as a device tensor, the adaptation's counters) of a run with adapt_mass > 0, and under adapt_dense (the
+    factor of the dense mass, the counters, True); None otherwise"""
     if not prop.get("adapt_mass"):
         return None
     with torch.cuda.device(tdev):
+        if prop.get("adapt_dense"):
+            return eng.get_dense_mass(torch.empty((eng.dim, eng.dim), dtype=torch.float64, device=tdev)), eng.get_dense_mass_adaptation(), True
         return eng.get_mass(torch.empty((eng.dim,), dtype=torch.float64, device=tdev))
 
 

@@ -377,6 +377,11 @@ struct tda_engine {
   // a fixed dense inverse mass W = L L^T of HMC / NUTS (tda_engine_set_dense_mass, tda_host_dense_mass.inc): configuration as well
   std::vector<double> dense_chol_h;  // [d][d], the lower-triangular factor L; empty: the diagonal mass above
   DevBuf<double> dense_chol;         // [2][DP][DP]: L and behind it L^T, zero outside the triangle and in the padding (uploaded by tda_engine_init)
+  // warm-up adaptation of that dense mass (tda_engine_set_dense_mass_adaptation, tda_host_dense_mass_adapt.inc): the count, the
+  // updates and the refusals are mass_n, mass_updates and mass_refused above (an engine adapts one kind of mass or the other)
+  int64_t dmass_W = 0;           // warm-up steps; 0: off
+  bool dmass_own_start = false;  // dense_chol_h is diag(sqrt(inv_mass)), put there by set_dense_mass_adaptation
+  DevBuf<double> dmass_a, dmass_S1, dmass_S2, dmass_work;  // [DP], [NC][DP], [NC][pairs][4][64], [DP][DP] (NC = ceil(N / 16) chunks)
   DevBuf<double> q_mean_d, lq, qzblk, qzblk2[2];
   double am_sd = 1.0;
   bool L_shared = true;
@@ -1422,6 +1427,7 @@ int64_t tda_release_cached_memory(void) { return (int64_t)g_pool.trim(); }
 // ---- the rest of the ABI, by family (textual includes: one translation unit) ----
 #include "tda_host_mass.inc"
 #include "tda_host_dense_mass.inc"
+#include "tda_host_dense_mass_adapt.inc"
 #include "tda_host_setup.inc"
 #include "tda_host_dreamz_archive.inc"
 #include "tda_host_state.inc"

@@ -10,6 +10,9 @@ int tda_engine_set_dense_mass(tda_engine* e, const double* chol) {
   if (!e) return fail(TDA_ERR_INVALID, "null engine");
   if (!e->prop_set || e->is_dreamz || !leapfrog_proposal(e->pp.kind))
     return fail(TDA_ERR_STATE, "set_proposal with kind TDA_PROP_HMC or TDA_PROP_NUTS must precede set_dense_mass");
+  if (e->dmass_W > 0)
+    return fail(TDA_ERR_STATE, "set_dense_mass on an engine that adapts a dense mass: tda_engine_set_dense_mass_adaptation took its starting factor when it "
+                               "was called (switch it off with warmup_steps = 0 first, set the factor, and switch it on again)");
   if (chol && e->mass_W > 0)
     return fail(TDA_ERR_STATE, "set_dense_mass on an engine that adapts its mass: tda_engine_set_mass_adaptation learns a diagonal mass during warm-up "
                                "(switch it off with warmup_steps = 0 first)");

@@ -338,7 +338,27 @@ int tda_engine_init(tda_engine* e, const double* theta0) {
     }
     e->mass_n = 0;
     e->mass_updates = 0;
-    if (leapfrog_proposal(e->pp.kind) && e->mass_W > 0) {  // the window's moments: state of a mass-adapting engine alone
+    if (leapfrog_proposal(e->pp.kind) && e->dmass_W > 0) {  // the window's sums: state of a dense-adapting engine alone
+      const size_t NC = (size_t)((e->N + DMASS_CH - 1) / DMASS_CH);
+      if ((rc = e->dmass_a.alloc((size_t)DP)) || (rc = e->dmass_S1.alloc(NC * DP)) || (rc = e->dmass_S2.alloc(NC * dmass_s2_doubles(DP))) ||
+          (rc = e->dmass_work.alloc((size_t)DP * DP)))
+        return rc;
+      HIP_TRY(hipMemsetAsync(e->dmass_a.p, 0, e->dmass_a.n * sizeof(double), e->stream));
+      HIP_TRY(hipMemsetAsync(e->dmass_S1.p, 0, e->dmass_S1.n * sizeof(double), e->stream));
+      HIP_TRY(hipMemsetAsync(e->dmass_S2.p, 0, e->dmass_S2.n * sizeof(double), e->stream));
+      HIP_TRY(hipMemsetAsync(e->dmass_work.p, 0, e->dmass_work.n * sizeof(double), e->stream));
+    } else {
+      e->dmass_a.release();
+      e->dmass_S1.release();
+      e->dmass_S2.release();
+      e->dmass_work.release();
+    }
+    if (leapfrog_proposal(e->pp.kind) && e->dmass_W > 0) {  // (its count of refusals)
+      if ((rc = e->mass_refused.alloc(1))) return rc;
+      HIP_TRY(hipMemsetAsync(e->mass_refused.p, 0, sizeof(unsigned int), e->stream));
+      e->mass_mean.release();
+      e->mass_M2.release();
+    } else if (leapfrog_proposal(e->pp.kind) && e->mass_W > 0) {  // the window's moments: state of a mass-adapting engine alone
       if ((rc = e->mass_mean.alloc((size_t)NP * DP)) || (rc = e->mass_M2.alloc((size_t)NP * DP)) || (rc = e->mass_refused.alloc(1))) return rc;
       HIP_TRY(hipMemsetAsync(e->mass_mean.p, 0, (size_t)NP * DP * sizeof(double), e->stream));
       HIP_TRY(hipMemsetAsync(e->mass_M2.p, 0, (size_t)NP * DP * sizeof(double), e->stream));

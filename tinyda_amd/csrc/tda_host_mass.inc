@@ -21,11 +21,14 @@ bool mass_window(int64_t P, int64_t p, int64_t* first, int64_t* end) {
   return false;
 }
 
-inline bool mass_warming(const tda_engine* e, int64_t t) { return e->mass_W > 0 && t < e->mass_W; }
+// (either kind of adaptation: the dense one, tda_host_dense_mass_adapt.inc, cuts the blocks and records the states in the same way)
+inline bool mass_warming(const tda_engine* e, int64_t t) { return (e->mass_W > 0 && t < e->mass_W) || (e->dmass_W > 0 && t < e->dmass_W); }
+int dense_mass_after_block(tda_engine* e, int64_t t, int64_t S, const double* rec);
 
 // behind the step kernel of the block [t, t + S) (inside one period while the mass adapts): fold its states if it lies in a
 // window, and pool the chains if the window ends with it.  rec: the block's states, [S][N][d]
 int mass_after_block(tda_engine* e, int64_t t, int64_t S, const double* rec) {
+  if (e->dmass_W > 0) return dense_mass_after_block(e, t, S, rec);
   const int64_t period = e->pp.period;
   int64_t first = 0, end = 0;
   if (!mass_warming(e, t) || !mass_window(e->mass_W / period, t / period, &first, &end) || t / period < first) return TDA_OK;
@@ -73,6 +76,9 @@ int tda_engine_set_mass_adaptation(tda_engine* e, int64_t warmup_steps) {
   if (!e) return fail(TDA_ERR_INVALID, "null engine");
   if (!e->prop_set || e->is_dreamz || !leapfrog_proposal(e->pp.kind))
     return fail(TDA_ERR_STATE, "set_proposal with kind TDA_PROP_HMC or TDA_PROP_NUTS must precede set_mass_adaptation");
+  if (warmup_steps != 0 && e->dmass_W > 0)
+    return fail(TDA_ERR_STATE, "set_mass_adaptation on an engine that adapts a dense mass: tda_engine_set_dense_mass_adaptation learns the whole matrix "
+                               "during warm-up (switch it off with warmup_steps = 0 first)");
   if (warmup_steps != 0 && !e->dense_chol_h.empty())
     return fail(TDA_ERR_STATE, "set_mass_adaptation on an engine with a dense mass: the warm-up learns a diagonal mass, tda_engine_set_dense_mass "
                                "fixed a dense one (switch it off with chol = NULL first)");

@@ -269,6 +269,8 @@ int tda_engine_set_proposal(tda_engine* e, const tda_proposal_params* p) {
   }
   e->mass_W = 0;  // (tda_engine_set_mass_adaptation follows a proposal that takes it)
   e->dense_chol_h.clear();  // (and so does tda_engine_set_dense_mass)
+  e->dmass_W = 0;  // (and tda_engine_set_dense_mass_adaptation)
+  e->dmass_own_start = false;
   if (p->C) e->prop_C_h.assign(p->C, p->C + (size_t)e->d * e->d);
   e->pp.C = nullptr;
   e->am_sd = p->sd > 0.0 ? p->sd : std::min(1.0, 2.4 * 2.4 / e->d);

@@ -298,6 +298,8 @@ int tda_engine_run(tda_engine* e, int64_t n_iter, const tda_outputs* out) {
     }
     }
 
+    if (int mrc = dense_mass_before_block(e, e->t)) return mrc;  // (the shift of a window of the dense adaptation: tda_host_dense_mass_adapt.inc)
+
     // ---- fused MH steps ----
     StepArgs sa{};
     fill_level(e, lv, sa);

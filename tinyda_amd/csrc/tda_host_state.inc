@@ -102,6 +102,17 @@ void enumerate_state(tda_engine* e, std::vector<StateItem>& v) {
     dev(e->mass_M2);
     dev(e->mass_refused);
   }
+  if (e->dmass_W > 0 && e->dmass_S1.p) {  // a dense-adapting HMC / NUTS engine alone (tinyda_amd_dense_mass_adaptation.h)
+    v.push_back({&e->dmass_W, sizeof e->dmass_W, false, true});  // (checked, not adopted, like the diagonal adaptation's)
+    v.push_back({&e->pp.period, sizeof e->pp.period, false, true});
+    host(&e->mass_n, sizeof e->mass_n);
+    host(&e->mass_updates, sizeof e->mass_updates);
+    dev(e->mass_refused);
+    dev(e->dmass_a);
+    dev(e->dense_chol);
+    dev(e->dmass_S1);
+    dev(e->dmass_S2);
+  }
   if (e->nlev > 1) {
     host(e->cnt, sizeof e->cnt);
     host(e->done, sizeof e->done);

@@ -12,6 +12,7 @@
 //   tda_kernels_pooled.h  k_moments_partial / final
 //   tda_kernels_ext.h     k_ext_propose / k_ext_accept (batched host-callback forward models)
 //   tda_kernels_mass.h    k_mass_accumulate / k_mass_update (warm-up adaptation of the diagonal mass of HMC / NUTS)
+//   tda_kernels_dense_mass.h  k_dense_mass_shift / accumulate / update (warm-up adaptation of the dense mass of HMC / NUTS)
 #pragma once
 #include "tda_kernels_mh.h"
 #include "tda_kernels_ml.h"
@@ -21,3 +22,4 @@
 #include "tda_kernels_aemd.h"
 #include "tda_kernels_wide.h"
 #include "tda_kernels_mass.h"
+#include "tda_kernels_dense_mass.h"

@@ -110,7 +110,7 @@ class Engine:
 
     def set_proposal(self, kind, C_=None, scaling=1.0, adaptive=False, gamma=1.01, period=100, sd=None,
                      epsilon=1e-6, t0=0, block_moments=False, q_mean=None, state_operator=None, noise_operator=None, spectrum=None,
-                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8, adapt_mass=0, dense_mass=None):
+                     n_leapfrog=None, inv_mass=None, max_depth=None, target_accept=0.8, adapt_mass=0, dense_mass=None, adapt_dense=False):
         Cm = None if C_ is None else _f64(C_)
         p = _lib.tda_proposal_params(C.sizeof(_lib.tda_proposal_params), kind, scaling, int(adaptive), period, gamma,
                                      _ptr(Cm), -1.0 if sd is None else sd, epsilon, t0, int(block_moments),
@@ -130,7 +130,11 @@ class Engine:
             self.set_nuts(max_depth, target_accept, inv_mass)
         if dense_mass is not None:  # HMC / NUTS: the Cholesky factor of a fixed dense inverse mass
             self.set_dense_mass(dense_mass)
-        if adapt_mass:  # HMC / NUTS: warm-up adaptation of the mass
+        if adapt_mass and adapt_dense:  # HMC / NUTS: warm-up adaptation of a dense mass, from the factor above or diag(sqrt(inv_mass))
+            self.set_dense_mass_adaptation(adapt_mass)
+        elif adapt_dense:
+            raise ValueError("adapt_dense=True needs adapt_mass > 0, the number of warm-up steps")
+        elif adapt_mass:  # HMC / NUTS: warm-up adaptation of the mass
             self.set_mass_adaptation(adapt_mass)
 
     def set_dense_mass(self, chol):
@@ -152,6 +156,19 @@ class Engine:
         L = np.empty((self.dim, self.dim))
         self._ck(self.lib.tda_engine_get_dense_mass(self.h, _ptr(L)))
         return L
+
+    def set_dense_mass_adaptation(self, warmup_steps):
+        """adapt a dense inverse mass of HMC / NUTS during the first `warmup_steps` steps, pooled over the engine's chains
+        (include/tinyda_amd_dense_mass_adaptation.h): a multiple of the period, at least two periods, 0: off.  After set_proposal
+        (and after set_dense_mass, if the start is dense), before init; get_dense_mass reads the factor in force"""
+        self._ck(self.lib.tda_engine_set_dense_mass_adaptation(self.h, int(warmup_steps)))
+
+    def get_dense_mass_adaptation(self):
+        """the counters of an initialised HMC / NUTS engine with a dense mass: dict(updates, window_steps, next_update (global step,
+        -1: none), refused (window ends that left the factor unchanged))"""
+        info = np.zeros(4, dtype=np.int64)
+        self._ck(self.lib.tda_engine_get_dense_mass_adaptation(self.h, _ptr(info)))
+        return dict(updates=int(info[0]), window_steps=int(info[1]), next_update=int(info[2]), refused=int(info[3]))
 
     def set_mass_adaptation(self, warmup_steps):
         """adapt the diagonal inverse mass of HMC / NUTS during the first `warmup_steps` steps, pooled over the engine's chains

@@ -64,7 +64,8 @@ def _mass_adaptation(run):
 
 
 # (A dense inverse mass of HMC / NUTS -- inv_mass [d, d], include/tinyda_amd_dense_mass.h -- needs no rule of its own: it is a
-# key of the proposal's description, `dense_mass`, and lowers or is refused with its sampler by the rules below.)
+# key of the proposal's description, `dense_mass`, and lowers or is refused with its sampler by the rules below.  Its warm-up
+# adaptation -- adapt_dense, include/tinyda_amd_dense_mass_adaptation.h -- is one more such key, and falls under the adapt_mass rule above.)
 def _hierarchy_size(run):
     if not 1 <= run.n_levels <= MAX_LEVELS or type(run.proposal) not in _DEVICE_PROPOSALS:
         return "more than %d levels (or none), or a proposal class the engine has no kernel for (%s)" % (MAX_LEVELS, type(run.proposal).__name__)

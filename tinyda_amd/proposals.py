@@ -311,6 +311,32 @@ def _mass_pool(mean, M2, n, inv_mass):
     return np.where(ok, w, inv_mass), int(np.sum(~ok))
 
 
+def _dense_mass_pool(S1, S2, n, N, chol):
+    """The window's end of include/tinyda_amd_dense_mass_adaptation.h ("Update") over the sums S1 [NC, d] and S2 [NC, d, d] (the
+    lower triangle is read) of NC chunks, n states of each of N chains, taken about any shift: -> (the new factor L, 0) or, where
+    the regularised covariance is not finite or np.linalg.cholesky fails, (chol, 1): the whole factor is kept."""
+    d = S1.shape[1]
+    with np.errstate(all="ignore"):
+        s1, s2 = np.zeros(d), np.zeros((d, d))
+        for c in range(S1.shape[0]):  # chunks in ascending order
+            s1, s2 = s1 + S1[c], s2 + S2[c]
+        T = float(n) * float(N)
+        m = s1 / T
+        C = (s2 - (T * m)[:, None] * m[None, :]) / (T - 1.0)
+        W = C * T / (T + 5.0)
+        W[np.diag_indices(d)] += 1e-3 * 5.0 / (T + 5.0)
+        W = np.tril(W) + np.tril(W, -1).T  # (only the lower triangle is ever formed)
+        if not np.all(np.isfinite(W)):
+            return chol, 1
+        try:
+            L = np.tril(np.linalg.cholesky(W))
+        except np.linalg.LinAlgError:
+            return chol, 1
+        if not (np.all(np.isfinite(L)) and np.all(np.diag(L) > 0.0)):
+            return chol, 1
+    return L, 0
+
+
 def dense_inv_mass(W):
     """A dense inverse mass of HMC / NUTS (include/tinyda_amd_dense_mass.h), validated: -> (W [d, d], its lower Cholesky factor L,
     W = L L^T).  W must be square, finite, exactly symmetric and positive definite (np.linalg.cholesky decides)."""
@@ -374,17 +400,26 @@ class HMC(MALA):
     include/tinyda_amd_dense_mass.h writes it out: its Cholesky factor is computed once and kept as `chol_inv_mass`, the momentum
     is held whitened, q = L^T p, and a leapfrog step is q += (e/2) L^T g; theta += e L q; q += (e/2) L^T g'.  It lowers wherever
     the diagonal mass lowers.  `adapt_mass` learns a diagonal and is refused beside it; `mass_from_samples` turns a pilot run
-    into such a matrix."""
+    into such a matrix.
+
+    `adapt_mass` = W with `adapt_dense=True` learns the dense inverse mass during warm-up instead, on the schedule above, as
+    include/tinyda_amd_dense_mass_adaptation.h writes it out: at a window's end the regularised covariance of the window's states
+    and its Cholesky factor replace `inv_mass` [d, d] and `chol_inv_mass`, or, where the covariance is not finite and positive
+    definite, the whole factor is kept and `mass_refused` goes up by one.  `inv_mass` (None, [d] or [d, d]) is the start.  On the
+    device the covariance is pooled over all chains of the engine; a host chain adapts from its own window alone."""
 
     alpha_star = 0.65
 
-    def __init__(self, scaling=0.1, n_leapfrog=8, inv_mass=None, adaptive=False, gamma=1.01, period=100, adapt_mass=0):
+    def __init__(self, scaling=0.1, n_leapfrog=8, inv_mass=None, adaptive=False, gamma=1.01, period=100, adapt_mass=0, adapt_dense=False):
         if int(n_leapfrog) != n_leapfrog or not 1 <= n_leapfrog <= 1024:
             raise ValueError("n_leapfrog must be an integer in 1 .. 1024, not %r" % (n_leapfrog,))
+        self.adapt_dense = bool(adapt_dense)
+        if self.adapt_dense and not adapt_mass:
+            raise ValueError("adapt_dense=True needs adapt_mass > 0, the number of warm-up steps: adapt_mass = %r" % (adapt_mass,))
         self.chol_inv_mass = None
         if inv_mass is not None and np.ndim(inv_mass) >= 2:
             inv_mass, self.chol_inv_mass = dense_inv_mass(inv_mass)
-            if adapt_mass:
+            if adapt_mass and not self.adapt_dense:
                 raise ValueError("adapt_mass = %r with a dense inv_mass: the warm-up adaptation learns a diagonal mass" % (adapt_mass,))
         elif inv_mass is not None:
             inv_mass = np.atleast_1d(np.asarray(inv_mass, dtype=np.float64)).copy()
@@ -398,6 +433,10 @@ class HMC(MALA):
         self._mass_windows = mass_windows(self.adapt_mass, period) if self.adapt_mass else []
         self._mass_n, self._mass_mean, self._mass_M2 = 0, None, None
         self.mass_updates, self.mass_refused = 0, 0
+        # the start of a dense adaptation, as the plan carries it: (the diagonal [d] or None, the factor [d, d] or None)
+        self._mass_start = (None if inv_mass is None or self.chol_inv_mass is not None else inv_mass.copy(),
+                            None if self.chol_inv_mass is None else self.chol_inv_mass.copy())
+        self._mass_shift = None
 
     def setup_proposal(self, **kwargs):
         super().setup_proposal(**kwargs)
@@ -405,9 +444,40 @@ class HMC(MALA):
             raise ValueError("inv_mass has %d entries for %d parameters" % (self.inv_mass.shape[0], self.d))
         if self.adapt_mass and self.inv_mass is None:
             self.inv_mass = np.ones(self.d)
+        if self.adapt_dense and self.chol_inv_mass is None:  # a diagonal start: L = diag(sqrt(w)), W = L L^T
+            self.chol_inv_mass = np.diag(np.sqrt(self.inv_mass))
+            self.inv_mass = self.chol_inv_mass @ self.chol_inv_mass.T
+
+    def _adapt_dense_mass(self, x):
+        """_adapt_mass under adapt_dense (include/tinyda_amd_dense_mass_adaptation.h with N = 1, one chunk): the state before a
+        window's first step is its shift; the sums of y = x - a and of y y^T over the window; at its end the new factor"""
+        s = self.t - 1
+        if s >= self.adapt_mass:
+            return
+        x = np.asarray(x, dtype=np.float64)
+        for first, end in self._mass_windows:
+            if first <= s < end:
+                y = x - self._mass_shift
+                self._mass_n += 1
+                self._mass_mean = self._mass_mean + y  # (S1 and S2 of the text)
+                self._mass_M2 = self._mass_M2 + y[:, None] * y[None, :]
+                if s + 1 == end:
+                    self.chol_inv_mass, refused = _dense_mass_pool(self._mass_mean[None, :], self._mass_M2[None, :, :], self._mass_n, 1, self.chol_inv_mass)
+                    self.inv_mass = self.chol_inv_mass @ self.chol_inv_mass.T
+                    self.mass_refused += refused
+                    self.mass_updates += 1
+                    self._mass_n = 0
+                    if self.adaptive:
+                        self.k = 0  # the step-size rule's gain is full again under the new metric
+                break
+        if any(s + 1 == first for first, _ in self._mass_windows):  # x is the state before the next window's first step
+            self._mass_shift = x.copy()
+            self._mass_n, self._mass_mean, self._mass_M2 = 0, np.zeros(self.d), np.zeros((self.d, self.d))
 
     def _adapt_mass(self, x):
         """fold the state of step self.t - 1 (steps counted from 0) into its window; at the window's end the new mass"""
+        if self.adapt_dense:
+            return self._adapt_dense_mass(x)
         s = self.t - 1
         if s >= self.adapt_mass:
             return
@@ -469,6 +539,10 @@ class HMC(MALA):
 
     def _lowered_mass(self, low):
         """the mass in a plan: `inv_mass` [d] or None, and under a dense mass `dense_mass`, its factor [d, d] (the key is there only then)"""
+        if self.adapt_dense:  # the start as it was given (a host run may have moved inv_mass since), and the switch
+            w, L = self._mass_start
+            low = dict(low, inv_mass=None if w is None else w.copy(), adapt_mass=self.adapt_mass, adapt_dense=True)
+            return low if L is None else dict(low, dense_mass=L.copy())
         if self.chol_inv_mass is not None:
             return dict(low, inv_mass=None, dense_mass=self.chol_inv_mass.copy())
         low = dict(low, inv_mass=None if self.inv_mass is None else self.inv_mass.copy())
@@ -496,16 +570,16 @@ class NUTS(HMC):
     momentum from np.random.standard_normal, the direction of a doubling from np.random.randint(2) and then its merge uniform
     from np.random.random, and one np.random.random per leaf of a subtree after its first.  `totals` counts what the device's
     proposal_state reports: n_leapfrog, n_divergent, n_max_depth, depth_sum.  `adapt_mass` is HMC's: warm-up adaptation of the
-    inverse mass, pooled over all chains on the device and per chain on the host.  A two-dimensional `inv_mass` is HMC's fixed
+    inverse mass, pooled over all chains on the device and per chain on the host, and with `adapt_dense=True` of a dense one.  A two-dimensional `inv_mass` is HMC's fixed
     dense inverse mass (include/tinyda_amd_dense_mass.h): the edges, the momentum sums and the checkpoints then hold the whitened
     momentum q = L^T p, and the U-turn test is a plain dot product of q's."""
 
-    def __init__(self, scaling=0.1, max_depth=8, inv_mass=None, adaptive=False, target_accept=0.8, gamma=1.01, period=100, adapt_mass=0):
+    def __init__(self, scaling=0.1, max_depth=8, inv_mass=None, adaptive=False, target_accept=0.8, gamma=1.01, period=100, adapt_mass=0, adapt_dense=False):
         if int(max_depth) != max_depth or not 1 <= max_depth <= 10:
             raise ValueError("max_depth must be an integer in 1 .. 10, not %r" % (max_depth,))
         if not 0.0 < target_accept < 1.0:
             raise ValueError("target_accept must lie in (0, 1), not %r" % (target_accept,))
-        super().__init__(scaling, 1, inv_mass, adaptive, gamma, period, adapt_mass)
+        super().__init__(scaling, 1, inv_mass, adaptive, gamma, period, adapt_mass, adapt_dense)
         self.n_leapfrog = None  # (chosen per step)
         self.max_depth, self.target_accept = int(max_depth), float(target_accept)
         self.alpha_star = self.target_accept
