@@ -497,7 +497,9 @@ int tda_engine_set_level_callback(tda_engine* e, int level, tda_forward_batch_fn
 /* Convergence diagnostics of a device-resident history (the reference hands its chains to ArviZ, diagnostics.py:6-111):
  * rank-normalised split bulk ESS and R-hat (Vehtari et al. 2021) of every parameter.  params: DEVICE
  * [n_steps][n_chains][dim] (layout of tda_outputs.params), the first `burnin` steps are dropped; ess, rhat: HOST [dim].
- * `stream` may be NULL. */
+ * `stream` may be NULL.  At least 8 kept draws (an odd middle one is dropped); infinities rank like any value; a parameter without
+ * variance has ess = rhat = NaN; a parameter with a NaN among its kept draws has ess = rhat = NaN, and no other parameter is
+ * touched by it. */
 int tda_diag_ess_rhat(int device, void* stream, const double* params, int64_t n_steps, int64_t n_chains, int32_t dim,
                       int64_t burnin, double* ess, double* rhat);
 

@@ -9,6 +9,7 @@ import pytest
 
 import tinyda_amd as tda
 from oracle import ess_oracle as eo
+from tests import extdiag
 
 
 def _ar1(rho, chains, n, seed):
@@ -99,3 +100,56 @@ def test_ess_summary_layout():
     s = tda.ess_summary(x, burnin=100)
     assert s["ess"].shape == (3,) and s["ess_min"] <= s["ess_median"]
     np.testing.assert_allclose(s["ess"][1], eo.ess_bulk(x[100:, :, 1].T), rtol=1e-9)
+
+
+# ---- the cases of tests/extdiag.py: the shapes and values at which the device code takes another path (tests/test_gpu_diag.py) ----
+def _columns_of(name):
+    if name in extdiag.SHAPES:
+        return extdiag.columns(extdiag.shape_history(name), extdiag.SHAPES[name][3])
+    return extdiag.columns(extdiag.nan_replaced() if name == "nan_one_parameter" else extdiag.edges()[name])
+
+
+@pytest.mark.parametrize("name", list(extdiag.SHAPES) + list(extdiag.EDGES))
+def test_no_case_sits_on_a_cut_of_geyers_sequence(name):
+    """every decision of the truncation is MARGIN away from zero, for every parameter (the NaN case: with the NaN replaced)"""
+    margins = [extdiag.admit(c) for c in _columns_of(name)]
+    print("%s: smallest margin %.3e" % (name, min(margins)))
+    assert min(margins) >= extdiag.MARGIN, margins
+    if name == "all_constant":
+        assert margins == [np.inf]
+
+
+@pytest.mark.parametrize("name", list(extdiag.SHAPES) + [n for n in extdiag.EDGES if n != "nan_one_parameter"])
+def test_product_numpy_matches_the_oracle_at_the_device_cases(name):
+    ess, rhat = extdiag.reference(name)
+    cols = _columns_of(name)
+    got_ess, got_rhat = np.array([tda.ess_bulk(c) for c in cols]), np.array([tda.rhat(c) for c in cols])
+    print("%s: largest deviation ess %.2e rhat %.2e" % (name, extdiag.deviation(got_ess, ess), extdiag.deviation(got_rhat, rhat)))
+    nan = name == "all_constant"  # the only case without an answer: NaN from both, a number everywhere else
+    assert np.all(np.isnan(ess) == nan) and np.all(np.isnan(rhat) == nan)
+    np.testing.assert_allclose(got_ess, ess, rtol=1e-9, equal_nan=nan)
+    np.testing.assert_allclose(got_rhat, rhat, rtol=1e-10, equal_nan=nan)
+
+
+def test_a_nan_makes_its_parameter_nan_and_no_other():
+    """the NumPy twin's NaN rule (the oracle has none): ESS and R-hat of the parameter that holds a NaN are NaN; the others are
+    what they are without it"""
+    cols = extdiag.columns(extdiag.edges()["nan_one_parameter"])
+    ess, rhat = extdiag.reference("nan_one_parameter")  # of the history with the NaN replaced
+    j_nan = extdiag.NAN_AT[2]
+    for j, c in enumerate(cols):
+        if j == j_nan:
+            assert np.isnan(c).sum() == 1 and np.isnan(tda.ess_bulk(c)) and np.isnan(tda.rhat(c))
+        else:
+            np.testing.assert_allclose(tda.ess_bulk(c), ess[j], rtol=1e-9)
+            np.testing.assert_allclose(tda.rhat(c), rhat[j], rtol=1e-10)
+
+
+def test_the_edge_cases_are_what_they_claim():
+    e = extdiag.edges()
+    z = e["signed_zeros"]
+    assert np.sum((z == 0) & np.signbit(z)) > 100 and np.sum((z == 0) & ~np.signbit(z)) > 100 and np.sum(z < 0) > 100
+    assert 10 <= np.unique(e["discrete"]).size <= 16
+    assert np.unique(e["one_chain_constant"][:, 5]).size == 1
+    assert np.isposinf(e["infinities"]).sum() == 1 and np.isneginf(e["infinities"]).sum() == 1
+    assert np.isnan(e["nan_one_parameter"]).sum() == 1 and e["nan_one_parameter"].shape[2] == 3

@@ -7,6 +7,8 @@
 // tie runs resolved by binary search in the sorted keys) -> normal scores -> one batched real FFT of all half-chains;
 // only the chain-AVERAGED autocovariance enters Geyer's sequence, so the power spectra are averaged before a single
 // inverse transform.  The folded R-hat needs a second sort of |x - median|.
+// A NaN among the kept draws of a parameter makes that parameter's ESS and R-hat NaN, as in the NumPy version: k_diag_rank hands
+// it a NaN score, which reaches the series' mean and variance and from there both estimates.  Other parameters are untouched.
 #include <hipcub/hipcub.hpp>
 #include <hipfft/hipfft.h>
 
@@ -40,6 +42,10 @@ __global__ void k_diag_rank(const double* __restrict__ sorted, const uint32_t* _
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= total) return;
   const double v = sorted[p];
+  if (v != v) {  // a NaN has no rank (the sort leaves it at either end): its score is NaN, and so is everything of this parameter
+    z[idx[p]] = v;
+    return;
+  }
   int64_t lo = 0, hi = p;  // first position holding v
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;

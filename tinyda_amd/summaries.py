@@ -274,7 +274,8 @@ def rhat(x):
 def ess_rhat_device(params, burnin=0, device=0, stream=None):
     """Bulk ESS and R-hat of every parameter of a DEVICE history [draws, chains, dim] (a torch tensor or anything with
     data_ptr()/shape), computed on the GPU (tda_diag_ess_rhat: hipCUB radix sort + hipFFT).  Same estimators as
-    ess_bulk / rhat above, which are the checker.  Returns dict(ess=[dim], rhat=[dim])."""
+    ess_bulk / rhat above, which are the checker.  Returns dict(ess=[dim], rhat=[dim]).  A parameter with a NaN among its kept
+    draws gets ess = rhat = NaN, as ess_bulk / rhat give it; the other parameters are unaffected."""
     import ctypes as C
 
     from . import _lib
